@@ -16,6 +16,11 @@ SI-SDR sufficient statistics -> all-reduce of the metric statistics over ranks (
 `python bench.py --gpus N` starts the N ranks itself (one process per GPU, RANK / LOCAL_RANK / WORLD_SIZE /
 MASTER_* set, before anything touches the GPU) unless it already runs under a launcher (WORLD_SIZE set, e.g.
 torch.distributed.run), in which case --gpus must agree with WORLD_SIZE.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (frames/s, ms_per_step, SI-SDR of the
+last step).  `--full` adds what takes runs of its own: per-kernel times and the chain's roofline from a profiled step,
+the HBM read probe, the other BASELINE configs, the bf16x3 parity mode, config 1 on the GPU and the CPU baseline.
+`--dump-outputs DIR` writes what the timed path returned in its last step (rank 0's utterances) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -50,10 +55,15 @@ def parse_args(argv=None):
     ap.add_argument("--rank-k", type=int, default=8)
     ap.add_argument("--precision", default="bf16", choices=["bf16x3", "bf16"],
                     help="decoder MFMA mode: bf16 (BASELINE config 2) or bf16x3 (3-term split, ~fp32 accuracy)")
-    ap.add_argument("--no-parity-mode", action="store_true", help="skip the extra bf16x3 measurement")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure beside the headline: profiled step (kernels, roofline, measured_hbm), HBM read probe, "
+                         "other BASELINE configs, bf16x3 parity mode, config 1 on the GPU, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (s_hat, n_hat, cost, SI-SDR statistics) as DIR/<name>.npy")
+    ap.add_argument("--no-parity-mode", action="store_true", help="--full: skip the extra bf16x3 measurement")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-slice-utts", type=int, default=16, help="utterances of the config-4 slice of the CPU baseline (0: skip)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the one-step measurements of the other BASELINE configs")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the one-step measurements of the other BASELINE configs")
     ap.add_argument("--force-store", action="store_true", help="sample store also in bf16x3 mode (float rows)")
     ap.add_argument("--no-store", action="store_true",
                     help="M-step / Wiener filter decode the samples again instead of streaming the chain's stored variances")
@@ -192,6 +202,35 @@ def cpu_baseline(F, K, niter, slice_utts=16):
     return out
 
 
+DUMP_BUDGET = 60 * 2 ** 20      # bytes of array data under --dump-outputs (the directory stays under 64 MB)
+
+
+def dump_outputs(d, outs, uids, T, stats):
+    """Write what the timed path returned in its last step: per batch (s_hat, n_hat, cost) from Reconstructor.enhance and
+    the all-reduced SI-SDR statistics.  Rows are utterances (ids in utterances.npy); a set larger than the budget is cut to
+    a fixed, seeded sample of utterances, so two builds run with the same arguments write the same rows."""
+    import numpy as np
+    import torch
+    s = torch.cat([o[0] for o in outs]).view(len(uids), T)
+    n = torch.cat([o[1] for o in outs]).view(len(uids), T)
+    cost = torch.cat([o[2] for o in outs])
+    stats = np.asarray(stats, dtype=np.float64)
+    per_utt = 2 * T * 4 + cost.shape[1] * 8 + 8
+    keep = min(len(uids), max(1, (DUMP_BUDGET - stats.nbytes) // per_utt))
+    rows = np.arange(len(uids)) if keep == len(uids) else np.sort(np.random.default_rng(0).choice(len(uids), keep, replace=False))
+    idx = torch.from_numpy(rows).to(s.device)
+    os.makedirs(d, exist_ok=True)
+    arrays = {"s_hat": s.index_select(0, idx).cpu().numpy().astype(np.float32),
+              "n_hat": n.index_select(0, idx).cpu().numpy().astype(np.float32),
+              "cost": cost.index_select(0, idx).cpu().numpy().astype(np.float64),
+              "utterances": np.asarray(uids, dtype=np.float64)[rows],
+              "si_sdr_stats": stats}
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+    note("outputs of the last timed step (%d of %d utterances, %.1f MB) written to %s"
+         % (keep, len(uids), sum(a.nbytes for a in arrays.values()) / 1e6, d))
+
+
 def main():
     args = parse_args()
     env_world = os.environ.get("WORLD_SIZE")
@@ -216,6 +255,8 @@ def main():
 
     if not args.dry_run and not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU (no CPU fallback)")
+    if args.dry_run and args.dump_outputs:
+        raise SystemExit("bench.py: --dump-outputs needs the hot path (not --dry-run)")
     # rehearsal aid for one-GPU boxes: VAENMF_BENCH_SHARE_GPU=1 with --backend gloo runs every rank's compute on GPU 0 and
     # the (tiny) collectives through gloo on host tensors -- the launcher, the sharding and the max-over-ranks clock on real
     # kernels; never the measured configuration (RCCL refuses two ranks on one device)
@@ -304,15 +345,18 @@ def main():
     rec, clf = make_rec(args.model, nfft, args.rank_k, args.precision, store)
     nsE, biE, nsW, biW = rec.nsE, rec.biE, rec.nsW, rec.biW
 
-    def enqueue(i, r=None, c=None, dd=None):
+    def enqueue(i, r=None, c=None, dd=None, outs=None):
         """One step's batches onto the GPU; nothing is read back (the host prepares the next step while this one runs).
-        Returns the per-batch Gram sums (device) and the last batch's cost (device)."""
+        Returns the per-batch Gram sums (device) and the last batch's cost (device); `outs` (a list) also receives every
+        batch's (s_hat, n_hat, cost)."""
         r, c, dd = r or rec, c if r else clf, dd or data
         grams, cost = [], None
         for bi, (wx, ws, wn, snr, counts) in enumerate(dd):
             uids = batches[bi] if dd is data else list(range(len(counts)))
             s_hat, n_hat, cost = r.enhance(wx, counts, seeds=[1000 * i + int(u) for u in uids], init_seed=i * 131 + bi, classifier=c)
             grams.append((vmet.gram3_batch_device(s_hat, ws, wn, counts), snr))      # 6 doubles per utterance, left on the device
+            if outs is not None:
+                outs.append((s_hat, n_hat, cost))
         return grams, cost
 
     def collect(steps_grams):
@@ -339,8 +383,9 @@ def main():
     note("timing %d step(s)" % args.steps)
     t0 = time.perf_counter()
     pending = []
+    last_outs = [] if args.dump_outputs else None       # (only the last step's outputs are held: the others free as before)
     for i in range(args.steps):                          # K steps enqueued back to back; their results are read inside the region
-        grams, cost = enqueue(args.warmup + i)
+        grams, cost = enqueue(args.warmup + i, outs=last_outs if i == args.steps - 1 else None)
         pending.append(grams)
     st = collect(pending)
     barrier()
@@ -353,6 +398,9 @@ def main():
         dist.all_reduce(nutt, op=dist.ReduceOp.SUM)
     dt = float(tmax.item())
     frames_per_utt = rec.frame_counts[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_outs, ids, T, st)
+    del last_outs
     m_step_path = {1: "stored sample variances (rows written by the chain, streamed by the M-step and the Wiener filter)",
                    2: "decode (the M-step decodes the samples again)"}.get(_lib.lib().vaenmf_plan_query(rec.eng._plan, _lib.Q_MSTEP_PATH), "?")
 
@@ -406,7 +454,8 @@ def main():
             raise KeyError("%s: no kernel matching '%s' (a renamed kernel? re-run tools/profile.sh and commit the summary)" % (src, sub))
         return hit[0]
 
-    ms, cn = profiled_step(rec, clf, data, args.warmup + args.steps, args.niter)
+    if args.full:
+        ms, cn = profiled_step(rec, clf, data, args.warmup + args.steps, args.niter)
 
     # ---- the other BASELINE configs (rank 0 of a 1-GPU run), one 64-utterance batch each: two untimed calls (the eager
     # one and the graph capture), then the median of three timed, synchronised calls on the REPLAYED graph; then a
@@ -414,7 +463,7 @@ def main():
     configs = []
     par = None
     cfg1_gpu = None
-    if world == 1 and not strong and rank == 0:
+    if args.full and world == 1 and not strong and rank == 0:
         del rec
         torch.cuda.empty_cache()
         b64 = [make_batch(list(range(BATCH)))]
@@ -501,17 +550,6 @@ def main():
         frames = n_total * frames_per_utt * args.steps
         value = frames / dt
         bpf, flop_row = algorithmic(F, args.niter, nsE, nsW)
-        rl = chain_roofline(ms, cn, F, frames_per_utt, [d_[4] for d_ in data], args.niter,
-                            type("R", (), {"nsE": nsE, "biE": biE, "nsW": nsW, "biW": biW}))
-        tag = args.precision if args.model == "M1" and nfft == 512 and args.rank_k == 8 else "%s_%s_f%d_k%d" % (args.precision, args.model, F, args.rank_k)
-        kern, traffic_src, terr = committed_traffic(tag)
-        rl["traffic"] = traffic_of(kern, "chain_kernel", traffic_src) if kern else None
-        rl["traffic_source"] = ("%s (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE passes of this command; not measured in this run)" % traffic_src) if kern else terr
-        rl["note"] = ("algorithmic decoder flops (1 proposal decode per MH step, %d flop/row) / HIP-event launch time of a profiled step "
-                      "outside the timed region; the bf16x3 mode issues 3 MFMAs per algorithmic product; valu_issue = the bound of the "
-                      "kernel's own instruction stream (v_exp/v_log/v_rcp_f32: 8.2 cycles per wave-instruction per SIMD, 1024 SIMDs, 2.4 GHz)" % flop_row)
-        kernels = {k: {"ms_total": round(ms[i], 3), "launches": int(cn[i])} for i, k in enumerate(KNAMES)}
-        iter_ms = sum(ms[i] / max(cn[i], 1) for i in range(4))
         workload = (("fixed %d-utterance set sharded over %d GPU(s) in batches of <= %d" % (n_total, world, BATCH)) if strong
                     else ("%d-utterance batch per GPU" % args.utts))
         out = {
@@ -526,49 +564,60 @@ def main():
                        "parallelism": "utterance-shard x%d (np.array_split, no collective in the loop)" % world},
             "collective_backend": backend,
             "em_graph_replayed": main_graph,
-            "roofline": rl,
             "hbm_equiv": {"algorithmic_bytes_per_frame": bpf, "achieved_GBps": value * bpf / 1e9, "frac_of_8TBps": value * bpf / PEAK_HBM,
                           "note": "SURVEY 8(d) B_utt CREDIT (fp32 sample variances written once, read by W-, H-, g-update and cost per "
-                                  "iteration): a credit, not a bandwidth -- the build moves fewer real bytes, see measured_hbm"},
+                                  "iteration): a credit, not a bandwidth -- the build moves fewer real bytes, see measured_hbm (--full)"},
             "m_step_path": m_step_path,
-            "kernels": kernels,
-            "kernels_note": "HIP events of rank 0's profiled step" + (" (the other ranks run the same kernels on their shards)" if world > 1 else ""),
             "si_sdr_mean_db": float(st[0, 0, 1] / max(st[0, 0, 0], 1)),
             "final_cost_mean": float(cost[:, -1].mean().item()),
         }
-        if kern:        # real HBM bytes per EM iteration from the committed PMC passes, against this run's kernel time per iteration
-            subs = [("chain_kernel",), ("wstats_stream", "wstats_rot", "wstats_fused"), ("hg_stream",), ("w_partial",), ("w_update", "w_final")]
-            per_iter, missing = 0.0, []
-            for alt in subs:
-                hit = [v["hbm_bytes_per_launch"] for k, v in kern.items() if any(a_ in k for a_ in alt)]
-                if hit:
-                    per_iter += hit[0]
-                elif alt[0] not in ("w_partial",):        # (fused into the W-statistics kernel in later builds)
-                    missing.append("/".join(alt))
-            out["measured_hbm"] = {"bytes_per_em_iteration": per_iter, "GBps": per_iter / (iter_ms * 1e-3) / 1e9,
-                                   "frac_of_8TBps": per_iter / (iter_ms * 1e-3) / PEAK_HBM, "kernels_missing_from_profile": missing,
-                                   "note": "rocprofv3 PMC bytes (%s, not this run) / this run's kernel time per EM iteration" % traffic_src}
-        else:
-            out["measured_hbm"] = {"error": terr}
-        # what this GPU delivers to a hand-written streaming read of the sample store's size (vaenmf_hbm_read_probe: 16 B per
-        # lane, 8 wavefronts per SIMD, grid = resident set), outside the timed region
-        pbuf = torch.empty(130 * 1024 * 1024, dtype=torch.float32, device=dev).normal_()
-        sink = torch.zeros(4, dtype=torch.int32, device=dev)
-        gb = C.c_double()
-        _lib.check(lib.vaenmf_hbm_read_probe(C.c_void_p(pbuf.data_ptr()), pbuf.numel() * 4, 10, C.c_void_p(sink.data_ptr()), C.byref(gb),
-                                              C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-        out["hbm_read_probe"] = {"GBps": gb.value, "bytes": pbuf.numel() * 4, "frac_of_8TBps": gb.value * 1e9 / PEAK_HBM,
-                                 "note": "hand-written HIP read kernel (aux.hip: 16 B per lane, 8 wavefronts per SIMD, 4 loads in flight per lane, grid = "
-                                         "resident set) over a 520 MB buffer, 10 sweeps: a measured rate of one kernel on this GPU, not a bound"}
-        del pbuf
-        if configs:
-            out["configs"] = configs
-        if par is not None:
-            out["parity_mode"] = par
-        if cfg1_gpu is not None:
-            out["config_1_gpu"] = cfg1_gpu
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(F, args.rank_k, args.niter, args.cpu_slice_utts)
+        if args.full:
+            rl = chain_roofline(ms, cn, F, frames_per_utt, [d_[4] for d_ in data], args.niter,
+                                type("R", (), {"nsE": nsE, "biE": biE, "nsW": nsW, "biW": biW}))
+            tag = args.precision if args.model == "M1" and nfft == 512 and args.rank_k == 8 else "%s_%s_f%d_k%d" % (args.precision, args.model, F, args.rank_k)
+            kern, traffic_src, terr = committed_traffic(tag)
+            rl["traffic"] = traffic_of(kern, "chain_kernel", traffic_src) if kern else None
+            rl["traffic_source"] = ("%s (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE passes of this command; not measured in this run)" % traffic_src) if kern else terr
+            rl["note"] = ("algorithmic decoder flops (1 proposal decode per MH step, %d flop/row) / HIP-event launch time of a profiled step "
+                          "outside the timed region; the bf16x3 mode issues 3 MFMAs per algorithmic product; valu_issue = the bound of the "
+                          "kernel's own instruction stream (v_exp/v_log/v_rcp_f32: 8.2 cycles per wave-instruction per SIMD, 1024 SIMDs, 2.4 GHz)" % flop_row)
+            iter_ms = sum(ms[i] / max(cn[i], 1) for i in range(4))
+            out["roofline"] = rl
+            out["kernels"] = {k: {"ms_total": round(ms[i], 3), "launches": int(cn[i])} for i, k in enumerate(KNAMES)}
+            out["kernels_note"] = "HIP events of rank 0's profiled step" + (" (the other ranks run the same kernels on their shards)" if world > 1 else "")
+            if kern:        # real HBM bytes per EM iteration from the committed PMC passes, against this run's kernel time per iteration
+                subs = [("chain_kernel",), ("wstats_stream", "wstats_rot", "wstats_fused"), ("hg_stream",), ("w_partial",), ("w_update", "w_final")]
+                per_iter, missing = 0.0, []
+                for alt in subs:
+                    hit = [v["hbm_bytes_per_launch"] for k, v in kern.items() if any(a_ in k for a_ in alt)]
+                    if hit:
+                        per_iter += hit[0]
+                    elif alt[0] not in ("w_partial",):        # (fused into the W-statistics kernel in later builds)
+                        missing.append("/".join(alt))
+                out["measured_hbm"] = {"bytes_per_em_iteration": per_iter, "GBps": per_iter / (iter_ms * 1e-3) / 1e9,
+                                       "frac_of_8TBps": per_iter / (iter_ms * 1e-3) / PEAK_HBM, "kernels_missing_from_profile": missing,
+                                       "note": "rocprofv3 PMC bytes (%s, not this run) / this run's kernel time per EM iteration" % traffic_src}
+            else:
+                out["measured_hbm"] = {"error": terr}
+            # what this GPU delivers to a hand-written streaming read of the sample store's size (vaenmf_hbm_read_probe: 16 B per
+            # lane, 8 wavefronts per SIMD, grid = resident set), outside the timed region
+            pbuf = torch.empty(130 * 1024 * 1024, dtype=torch.float32, device=dev).normal_()
+            sink = torch.zeros(4, dtype=torch.int32, device=dev)
+            gb = C.c_double()
+            _lib.check(lib.vaenmf_hbm_read_probe(C.c_void_p(pbuf.data_ptr()), pbuf.numel() * 4, 10, C.c_void_p(sink.data_ptr()), C.byref(gb),
+                                                  C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            out["hbm_read_probe"] = {"GBps": gb.value, "bytes": pbuf.numel() * 4, "frac_of_8TBps": gb.value * 1e9 / PEAK_HBM,
+                                     "note": "hand-written HIP read kernel (aux.hip: 16 B per lane, 8 wavefronts per SIMD, 4 loads in flight per lane, grid = "
+                                             "resident set) over a 520 MB buffer, 10 sweeps: a measured rate of one kernel on this GPU, not a bound"}
+            del pbuf
+            if configs:
+                out["configs"] = configs
+            if par is not None:
+                out["parity_mode"] = par
+            if cfg1_gpu is not None:
+                out["config_1_gpu"] = cfg1_gpu
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline(F, args.rank_k, args.niter, args.cpu_slice_utts)
         print(json.dumps(out))
     if use_pg:
         dist.destroy_process_group()

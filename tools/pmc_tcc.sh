@@ -4,7 +4,7 @@ set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/pmctcc
 rm -rf $OUT; mkdir -p $OUT
-ARGS="bench.py --steps 1 --warmup 0 --niter 6 --no-cpu-baseline --no-parity-mode --no-configs"
+ARGS="bench.py --full --steps 1 --warmup 0 --niter 6 --no-cpu-baseline --no-parity-mode --no-configs"
 timeout -k 10 200 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum --output-format csv -d $OUT/a -- python $ARGS > $OUT/a.log 2>&1; echo "a rc=$?"
 timeout -k 10 200 rocprofv3 --pmc TCP_TCC_READ_REQ_sum TCP_PENDING_STALL_CYCLES_sum TCP_TCC_READ_REQ_LATENCY_sum TCP_TOTAL_CACHE_ACCESSES_sum --output-format csv -d $OUT/b -- python $ARGS > $OUT/b.log 2>&1; echo "b rc=$?"
 python - <<'PY'

@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 TAG=$1; shift
 OUT=gpurun_out/prof_r3_$TAG
 rm -rf $OUT; mkdir -p $OUT
-B="--no-cpu-baseline --no-parity-mode --no-configs $*"
+B="--full --no-cpu-baseline --no-parity-mode --no-configs $*"
 echo "python bench.py $B" > $OUT/command.txt
 run() { name=$1; shift; timeout -k 10 300 rocprofv3 "$@" > $OUT/$name.log 2>&1; echo "$name rc=$?"; }
 run bench_trace --kernel-trace --stats --output-format csv -d $OUT/trace -- python bench.py --steps 2 --warmup 1 $B
