@@ -31,48 +31,17 @@ __device__ long long g_wc_stamp[32];
 #define WC_STAMP(slot)
 #define WC_STAMP_FLUSH
 #endif
-#ifndef VN_WC_SPREAD
-#define VN_WC_SPREAD 1      // wave tiles spread over the CUs first (one 4 s utterance through the drop-in classes: 80.5 -> 69.0 ms; the 64-utterance batch: unchanged)
-#endif
-#ifndef VN_PF
-#define VN_PF 1
-#endif
-#ifndef VN_PACKED
-#define VN_PACKED 1
-#endif
-#ifndef VN_ST_AUX
-#define VN_ST_AUX 0      // cache policy of the sample-variance row stores (2 = nt)
-#endif
-#ifndef VN_PFL
-#define VN_PFL 2      // bf16x3 mode, F > 80: tiles of W3-lo fragments (streamed from L2, ~1 us away) in flight ahead of their MFMAs -- with one
-                      // tile the single wavefront of a SIMD sat out the L2 latency once per bin tile (1.00 -> 0.89 ms per launch)
-#endif
-#ifndef VN_PFL_HOIST
-#define VN_PFL_HOIST 2     // of those, tiles requested at the top of the evaluation, two layers before their use (registers live through the
-                           // hidden layers: 2 + 2 fits the 512 registers, 3 + 1 spills; 132.5 -> 131.8 ms per bf16x3 step)
-#endif
-#ifndef VN_TPM
-#define VN_TPM 2      // transcendentals scheduled right behind each MFMA (a packed instruction waits for a matrix instruction in flight); 0: mixed with the other VALU work
-#endif
-#ifndef VN_TPR
-#define VN_TPR 1
-#endif
-#ifndef VN_VPER
-#define VN_VPER 8
-#endif
-#ifndef VN_SB
-#define VN_SB __builtin_amdgcn_sched_barrier(0)
-#endif
-
 namespace {
 
 constexpr int NK = HID / 32;      // k-steps over a hidden layer
 constexpr int NTH = HID / 16;     // feature tiles of a hidden layer
 constexpr int WT_FRAMES = 16;     // frames per wavefront
 constexpr unsigned WC_OOB = 0xF0000000u;   // byte offset behind every buffer of the chain (the host keeps them below 3.5 GB)
-#ifndef VN_WC_WAVES_BF16
-#define VN_WC_WAVES_BF16 8
-#endif
+constexpr int WC_PF = 1;          // tiles of weight fragments (and bias) in flight ahead of the MFMAs that use them
+// bf16x3 mode, F > 80: tiles of W3-lo fragments (streamed from L2, ~1 us away) in flight ahead of their MFMAs -- with one
+// tile the single wavefront of a SIMD sat out the L2 latency once per bin tile (1.00 -> 0.89 ms per launch)
+constexpr int WC_PFL = 2;
+constexpr int WC_ST_AUX = 0;      // cache policy of the sample-variance row stores (2 = nt)
 
 struct WcArgs {
   const __bf16 *w1f, *w2f, *w3f;   // fragment order [tile][kstep][part hi/lo][lane][8]; w3f in the chain's bin order
@@ -135,18 +104,11 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // Two elements per non-transcendental instruction (v_pk_add/mul/fma_f32): next to transcendentals a packed instruction
 // costs the issue slot of a plain one (tools/ubench/overlap.hip: 4.4 against 4.2 ticks, for twice the work).
 __device__ __forceinline__ f32x4 tanh4(const f32x4 a) {
-#if VN_PACKED
   const f32x2 one = {1.f, 1.f}, m2 = {-2.f, -2.f};
   const f32x2 d0 = f32x2{fast_exp(a[0]), fast_exp(a[1])} + one, d1 = f32x2{fast_exp(a[2]), fast_exp(a[3])} + one;
   const f32x2 r0 = {fast_rcp(d0[0]), fast_rcp(d0[1])}, r1 = {fast_rcp(d1[0]), fast_rcp(d1[1])};
   const f32x2 h0 = m2 * r0 + one, h1 = m2 * r1 + one;
   return f32x4{h0[0], h0[1], h1[0], h1[1]};
-#else
-  f32x4 h;
-#pragma unroll
-  for (int t = 0; t < 4; ++t) h[t] = fast_tanh(a[t]);
-  return h;
-#endif
 }
 template <bool SPLIT>
 __device__ __forceinline__ f32x4 mma(const bf16x8 whi, const bf16x8 wlo, const bf16x8 ahi, const bf16x8 alo, f32x4 acc) {
@@ -236,12 +198,9 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   // wave tile of (workgroup b, wavefront w, round i): (i NWAVES + w) gridDim + b -- a batch with fewer tiles than wavefront
   // slots (one utterance through the drop-in classes: 32 tiles) spreads one wavefront per CU instead of filling four
-  // workgroups, and a lone wavefront has its SIMD's issue slots to itself
-#if VN_WC_SPREAD
+  // workgroups, and a lone wavefront has its SIMD's issue slots to itself (one 4 s utterance through the drop-in classes:
+  // 80.5 -> 69.0 ms; the 64-utterance batch: unchanged)
   for (int wt = wave * (int)gridDim.x + (int)blockIdx.x; wt < a.n_wtiles; wt += (int)gridDim.x * NWAVES) {
-#else
-  for (int wt = blockIdx.x * NWAVES + wave; wt < a.n_wtiles; wt += gridDim.x * NWAVES) {
-#endif
     const int utt = a.wt_utt[wt], n0 = a.wt_n0[wt], cnt = a.wt_cnt[wt];
     const bool fvalid = c < cnt;
     const int nrow = n0 + (fvalid ? c : cnt - 1);          // idle lanes shadow the last frame (no stores)
@@ -360,8 +319,7 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
       //   frag_lo(t, s, lo): the lo fragments (bf16x3 mode), PFL tiles ahead
       auto run_layer = [&](auto nks_c, auto ntiles_c, auto pfl_c, auto frag, auto frag_lo, auto frag_lo_pro, auto bias, auto bop, auto epi) {
         constexpr int NKS = decltype(nks_c)::value, N = decltype(ntiles_c)::value;
-        // VN_PF tiles of weight fragments (and bias) in flight ahead of the MFMAs that use them
-        constexpr int PF = VN_PF, NB = PF + 1;
+        constexpr int PF = WC_PF, NB = PF + 1;
         constexpr int PFL = SPLIT ? decltype(pfl_c)::value : 0, NBL = PFL + 1;
         bf16x8 wh[NB][NKS], wl[NBL][NKS];
         f32x4 acc[2], bq[NB];
@@ -403,25 +361,24 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
           // order inside the region: every MFMA of the tile followed by a share of the previous tile's epilogue.  A wave
           // whose next instruction is an MFMA waiting for the matrix pipe (or for the accumulator of the MFMA before it)
           // holds the SIMD's vector issue port -- measured: a wave of back-to-back MFMAs starves its SIMD partner's VALU
-          // stream (tools/ubench/overlap.hip) -- so the MFMAs are spaced by VALU work of the same wave
+          // stream (tools/ubench/overlap.hip) -- so the MFMAs are spaced by VALU work of the same wave.  Transcendentals
+          // are scheduled right behind each MFMA (a packed instruction waits for a matrix instruction in flight)
           if (NKS > 1 && t > 0 && t < N) {
+            constexpr int VPER = 8, TPM = 2;      // VALU instructions per MFMA, of them transcendentals first
 #pragma unroll
             for (int s = 0; s < NKS; ++s) {
               __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);          // one MFMA
-#if VN_TPM > 0
-              __builtin_amdgcn_sched_group_barrier(0x400, VN_TPM, 0);     // transcendentals first (see VN_TPM)
-              __builtin_amdgcn_sched_group_barrier(0x002, VN_VPER - VN_TPM, 0);
-#else
-              __builtin_amdgcn_sched_group_barrier(0x402, VN_VPER, 0);    // VALU / transcendental
-#endif
+              __builtin_amdgcn_sched_group_barrier(0x400, TPM, 0);        // transcendentals
+              __builtin_amdgcn_sched_group_barrier(0x002, VPER - TPM, 0);
             }
           }
-          if (VN_TPR <= 1 || (t % VN_TPR) == VN_TPR - 1 || t == N) VN_SB;      // VN_TPR tiles per scheduling region
+          __builtin_amdgcn_sched_barrier(0);      // one tile per scheduling region
         }
       };
       // bf16x3 mode, W3-lo streamed from L2: the first NHOIST tiles' lo fragments are requested here, two layers before their
       // use (the single wavefront of a SIMD otherwise sits out one L2 round trip per evaluation at the head of the output layer)
-      constexpr int NHOIST = (SPLIT && !LOL && !M2) ? VN_PFL_HOIST : 0;      // (M2 keeps its 32 bias registers instead)
+      // (registers live through the hidden layers: 2 + 2 fits the 512 registers, 3 + 1 spills; 132.5 -> 131.8 ms per bf16x3 step)
+      constexpr int NHOIST = (SPLIT && !LOL && !M2) ? 2 : 0;      // (M2 keeps its 32 bias registers instead)
       bf16x8 lo_pre[NHOIST > 0 ? NHOIST : 1][NK];
       if (NHOIST > 0) {
 #pragma unroll
@@ -445,7 +402,7 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
           bl[0][2] = pk2(zz[4] - bf_lo(bh[0][2]), zz[5] - bf_hi(bh[0][2]));
           bl[0][3] = pk2(zz[6] - bf_lo(bh[0][3]), zz[7] - bf_hi(bh[0][3]));
         }
-        run_layer(std::integral_constant<int, 1>{}, std::integral_constant<int, NTH>{}, std::integral_constant<int, VN_PF>{},
+        run_layer(std::integral_constant<int, 1>{}, std::integral_constant<int, NTH>{}, std::integral_constant<int, WC_PF>{},
                   [&](int t, int, bf16x8& hi) { hi = *reinterpret_cast<const bf16x8*>(smem + L::W1 + t * PARTS * 1024 + l16); },
                   [&](int t, int, bf16x8& lo) { lo = *reinterpret_cast<const bf16x8*>(smem + L::W1 + t * PARTS * 1024 + (SPLIT ? 1024 : 0) + l16); },
                   [&](int t, int, bf16x8& lo) { lo = *reinterpret_cast<const bf16x8*>(smem + L::W1 + t * PARTS * 1024 + (SPLIT ? 1024 : 0) + l16); },
@@ -465,7 +422,7 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
 #pragma unroll
         for (int s = 0; s < NK; ++s) { bh[s] = ch[s]; if (SPLIT) bl[s] = cl[s]; }
       } else
-      run_layer(std::integral_constant<int, NK>{}, std::integral_constant<int, NTH>{}, std::integral_constant<int, VN_PF>{},
+      run_layer(std::integral_constant<int, NK>{}, std::integral_constant<int, NTH>{}, std::integral_constant<int, WC_PF>{},
                 [&](int t, int s, bf16x8& hi) { hi = *reinterpret_cast<const bf16x8*>(smem + L::W2 + (t * NK + s) * PARTS * 1024 + l16); },
                 [&](int t, int s, bf16x8& lo) { lo = *reinterpret_cast<const bf16x8*>(smem + L::W2 + (t * NK + s) * PARTS * 1024 + (SPLIT ? 1024 : 0) + l16); },
                 [&](int t, int s, bf16x8& lo) { lo = *reinterpret_cast<const bf16x8*>(smem + L::W2 + (t * NK + s) * PARTS * 1024 + (SPLIT ? 1024 : 0) + l16); },
@@ -475,11 +432,9 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
       WC_STAMP(2);
       // ---- output layer: each finished tile straight into the energy epilogue
       double e = 0.0;
-      float ef = 0.f;
       f32x2 pl2 = {0.f, 0.f}, px2 = {0.f, 0.f};
-      (void)ef;
       unsigned pk_even0 = 0, pk_even1 = 0;
-      run_layer(std::integral_constant<int, NK>{}, std::integral_constant<int, MAXT>{}, std::integral_constant<int, (SPLIT && !LOL) ? VN_PFL : VN_PF>{},
+      run_layer(std::integral_constant<int, NK>{}, std::integral_constant<int, MAXT>{}, std::integral_constant<int, (SPLIT && !LOL) ? WC_PFL : WC_PF>{},
                 [&](int t, int s, bf16x8& hi) {
                   if (GT > 0 && t < GT) hi = gfr[t < GT ? t : 0][s];
                   else if (HIALL || t - GT < n_hi) hi = *reinterpret_cast<const bf16x8*>(smem + L::W3 + ((t - GT) * NK + s) * 1024 + l16);
@@ -489,7 +444,7 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
                   if (LOL) lo = *reinterpret_cast<const bf16x8*>(w3lo_lds + (t * NK + s) * 1024 + l16);
                   else lo = *reinterpret_cast<const bf16x8*>(w3g + (size_t)((t * NK + s) * 2 + 1) * 1024 + l16);
                 },
-                [&](int t, int s, bf16x8& lo) {           // the first tiles' lo fragments: requested at the top of the evaluation (VN_PFL_HOIST)
+                [&](int t, int s, bf16x8& lo) {           // the first tiles' lo fragments: requested at the top of the evaluation (NHOIST)
                   if (LOL) lo = *reinterpret_cast<const bf16x8*>(w3lo_lds + (t * NK + s) * 1024 + l16);
                   else if (t < NHOIST) lo = lo_pre[t < NHOIST ? t : 0][s];
                   else lo = *reinterpret_cast<const bf16x8*>(w3g + (size_t)((t * NK + s) * 2 + 1) * 1024 + l16);
@@ -501,7 +456,6 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
                   f32x4 ev;
 #pragma unroll
                   for (int j = 0; j < 4; ++j) ev[j] = fast_exp(acc[j]);
-#if VN_PACKED
                   {
                     // pairs (bin 0, bin 2) and (bin 1, bin 3): the two pairs are the two lanes of the packed instructions
                     const f32x2 g2 = {gn, gn};
@@ -511,55 +465,27 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
                     const f32x2 rc = {fast_rcp(pp[0]), fast_rcp(pp[1])};
                     px2 = (x2[t].lo * v1 + x2[t].hi * v0) * rc + px2;
                   }
-#else
-                  float pl = 0.f, px = 0.f;
-#pragma unroll
-                  for (int j = 0; j < 4; j += 2) {
-                    const float v0 = gn * ev[j] + vb[t][j];
-                    const float v1 = gn * ev[j + 1] + vb[t][j + 1];
-                    const float pp = v0 * v1;
-                    pl += fast_log2(pp);
-                    px += (x2[t][j] * v1 + x2[t][j + 1] * v0) * fast_rcp(pp);
-                  }
-#endif
                   if (DOST) {
                     if (SPLIT) {
-                      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, ev), vrs, voff + 16u * q + 64u * t, 0, VN_ST_AUX);
+                      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, ev), vrs, voff + 16u * q + 64u * t, 0, WC_ST_AUX);
                     } else {
                       const unsigned p0 = pk2(ev[0], ev[1]), p1 = pk2(ev[2], ev[3]);
                       if (t < Tm) {
                         if ((t & 1) == 0) { pk_even0 = p0; pk_even1 = p1; }
-                        else __builtin_amdgcn_raw_buffer_store_b128(u32x4{pk_even0, pk_even1, p0, p1}, vrs, voff + 16u * q + 64u * (t >> 1), 0, VN_ST_AUX);
+                        else __builtin_amdgcn_raw_buffer_store_b128(u32x4{pk_even0, pk_even1, p0, p1}, vrs, voff + 16u * q + 64u * (t >> 1), 0, WC_ST_AUX);
                       } else {
-                        __builtin_amdgcn_raw_buffer_store_b64(u32x2{p0, p1}, vrs, voff + 8u * q + 32u * t, 0, VN_ST_AUX);
+                        __builtin_amdgcn_raw_buffer_store_b64(u32x2{p0, p1}, vrs, voff + 8u * q + 32u * t, 0, WC_ST_AUX);
                       }
                     }
                   }
-#if VN_PACKED
                   if ((t & 1) == 1) {          // fp32 over two tiles, fp64 across them
                     e += (double)((pl2[0] + pl2[1]) * LN2_F + (px2[0] + px2[1]));
                     pl2 = px2 = f32x2{0.f, 0.f};
                   }
-#else
-                  ef += pl * LN2_F + px;
-                  if ((t & 1) == 1) { e += (double)ef; ef = 0.f; }
-#endif
                 });
-#if VN_PACKED
       e += (double)((pl2[0] + pl2[1]) * LN2_F + (px2[0] + px2[1]));
-#else
-      e += (double)ef;
-#endif
       WC_STAMP(3);
-#ifdef VN_EXP_F32SUM
-      return (double)sum_rows4((float)e);
-#elif defined(VN_EXP_PRIO)
-      __builtin_amdgcn_s_setprio(3);
-      const double r_ = sum_rows4_d(e);
-      return r_;
-#else
       return sum_rows4_d(e);
-#endif
     };
 
     double Ecur = 0.0;
@@ -605,9 +531,6 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
 #pragma unroll
         for (int t = 0; t < 8; ++t) zp[t] = z[t];
       }
-#ifdef VN_EXP_PRIO
-      __builtin_amdgcn_s_setprio(0);
-#endif
       WC_STAMP(0);
       const int slot = !STORE ? -1 : (re ? a.nsamples : (m >= a.burnin ? m - a.burnin : ((m < 0 && a.burnin == 0) ? a.nsamples : -1)));
       double Ep;
@@ -862,9 +785,9 @@ __global__ __launch_bounds__(256, 1) void wchain4_kernel(const WcArgs a) {
           const unsigned t = (unsigned)tile_of(i);
           if (i < 2 * PPW) {
             if ((i & 1) == 0) { pk_even0 = p0; pk_even1 = p1; }
-            else __builtin_amdgcn_raw_buffer_store_b128(u32x4{pk_even0, pk_even1, p0, p1}, vrs, voff + 16u * q + 64u * (t >> 1), 0, VN_ST_AUX);
+            else __builtin_amdgcn_raw_buffer_store_b128(u32x4{pk_even0, pk_even1, p0, p1}, vrs, voff + 16u * q + 64u * (t >> 1), 0, WC_ST_AUX);
           } else {
-            __builtin_amdgcn_raw_buffer_store_b64(u32x2{p0, p1}, vrs, voff + 8u * q + 32u * t, 0, VN_ST_AUX);
+            __builtin_amdgcn_raw_buffer_store_b64(u32x2{p0, p1}, vrs, voff + 8u * q + 32u * t, 0, WC_ST_AUX);
           }
         }
         if ((i & 1) == 1 || i == 2 * PPW) {     // fp32 over a pair's two tiles (the odd last tile alone), as wchain_kernel
@@ -983,40 +906,23 @@ int wc_launch(const WcArgs& a, int grid, size_t lds, hipStream_t st) {
 // M1 runs NW1 wavefronts per workgroup; M2 the same (at 8 the per-frame layer-1 bias rows live in LDS: b1_lds)
 template <int MAXT, bool EXACT, bool SPLIT, int NW1, bool LOL, int GT = 0>
 int wc_launch_s(const WcArgs& a, int nwt, int n_sms, size_t lds, hipStream_t st) {
-  const int nw = NW1;
-#if VN_WC_SPREAD
   int grid = nwt;                                       // (wave tiles spread over the CUs first, then over a workgroup's wavefronts)
-#else
-  int grid = (nwt + nw - 1) / nw;
-#endif
   if (grid > n_sms) grid = n_sms;                       // one workgroup per CU (LDS), wave tiles in a grid-stride loop
-  if (a.B1) {
-#if !defined(VN_DEV_FAST) || defined(VN_DEV_M2)
+  if (a.B1)
     return a.VsS ? wc_launch<MAXT, EXACT, SPLIT, true, NW1, LOL, true, true, GT>(a, grid, lds, st)
                  : wc_launch<MAXT, EXACT, SPLIT, false, NW1, LOL, true, true, GT>(a, grid, lds, st);
-#else
-    return -1;
-#endif
-  }
   return a.VsS ? wc_launch<MAXT, EXACT, SPLIT, true, NW1, LOL, true, false, GT>(a, grid, lds, st)
                : wc_launch<MAXT, EXACT, SPLIT, false, NW1, LOL, true, false, GT>(a, grid, lds, st);
 }
 
 }  // namespace
 
-// dev / test switch: VAENMF_WCHAIN4=0 keeps small batches on wchain_kernel (read per call)
-static bool wc4_enabled() {
-  const char* e = getenv("VAENMF_WCHAIN4");
-  return !(e && e[0] == '0');
-}
-
 // Shapes the wave-private chain covers (the rest runs engine.hip's team kernel): every W3 hi fragment in LDS
 bool vn_wchain_supported(const vaenmf_plan* p) {
   // up to 17 bin tiles (F <= 272) in both precision modes; F = 513..528 (33 tiles, the reference scripts' 1024-pt STFT)
   // in bf16 mode with four tiles' fragments streamed from L2
   if (p->NT3c > 17 && !(p->NT3c == 33 && p->cfg.precision == VAENMF_PREC_BF16)) return false;
-  const char* e = getenv("VAENMF_TEAM_CHAIN");          // dev / test override: force the team kernel of engine.hip
-  return !(e && e[0] == '1');
+  return !vn_switches().team_chain;
 }
 
 // The wave chain addresses every per-frame buffer through a buffer resource with a 32-bit byte offset per lane and marks
@@ -1056,13 +962,13 @@ int vn_launch_wchain(vaenmf_plan* p, const VnChainCall& cc, hipStream_t st) {
   constexpr int GT33 = 4;                                // F = 513: bin tiles whose fragments stay in global memory
   const size_t w3hi = (size_t)(p->NT3c == 33 ? p->NT3c - GT33 : p->NT3c) * NK * 1024;
   const bool lol = split && p->NT3c <= 5;              // bf16x3: the lo fragments of W3 fit in LDS up to 5 tiles (F <= 80), else they stream from L2
-  constexpr int NW_BF16 = VN_WC_WAVES_BF16, NW_X3 = 4;
+  constexpr int NW_BF16 = 8, NW_X3 = 4;
   const int nwaves = (split || p->NT3c == 33) ? 4 : NW_BF16;
   a.b1_lds = (int)(fixed + w3hi * (lol ? 2 : 1));
   const size_t lds = (size_t)a.b1_lds + ((cc.B1 && nwaves == 8) ? (size_t)nwaves * NTH * 512 : 0);
   VN_REQUIRE(lds <= (size_t)WC_LDS_LIMIT, "wave chain: %zu bytes of LDS needed", lds);
   // small batches (at most one wave tile per CU) in bf16 mode at 17 / 33 bin tiles: four wavefronts per wave tile (wchain4_kernel)
-  if (!split && (p->NT3c == 17 || p->NT3c == 33) && p->n_wtiles <= p->n_sms && wc4_enabled()) {
+  if (!split && (p->NT3c == 17 || p->NT3c == 33) && p->n_wtiles <= p->n_sms && vn_switches().wchain4) {
     const size_t lds4 = 2 * 4 * 64 * 16 + 20 * 64 * 4;          // exchange areas only
     const int grid = p->n_wtiles;
     auto go = [&](auto* fn) -> int {
@@ -1083,15 +989,12 @@ int vn_launch_wchain(vaenmf_plan* p, const VnChainCall& cc, hipStream_t st) {
     return 0;
   }
   // wavefronts per workgroup: 8 (two per SIMD, 256 registers each) in bf16 mode, 4 (512 registers) in bf16x3 mode
-  int rc = -1;
+  int rc;
   if (p->NT3c == 33)     rc = wc_launch_s<33, true, false, 4, false, GT33>(a, p->n_wtiles, p->n_sms, lds, st);
   else if (p->NT3c == 17) rc = split ? wc_launch_s<17, true, true, NW_X3, false>(a, p->n_wtiles, p->n_sms, lds, st) : wc_launch_s<17, true, false, NW_BF16, false>(a, p->n_wtiles, p->n_sms, lds, st);
   else if (p->NT3c == 5) rc = split ? wc_launch_s<5, true, true, NW_X3, true>(a, p->n_wtiles, p->n_sms, lds, st)   : wc_launch_s<5, true, false, NW_BF16, false>(a, p->n_wtiles, p->n_sms, lds, st);
-#ifndef VN_DEV_FAST
   else if (p->NT3c < 5)  rc = split ? wc_launch_s<5, false, true, NW_X3, true>(a, p->n_wtiles, p->n_sms, lds, st)  : wc_launch_s<5, false, false, NW_BF16, false>(a, p->n_wtiles, p->n_sms, lds, st);
   else                   rc = split ? wc_launch_s<17, false, true, NW_X3, false>(a, p->n_wtiles, p->n_sms, lds, st) : wc_launch_s<17, false, false, NW_BF16, false>(a, p->n_wtiles, p->n_sms, lds, st);
-#endif
-  VN_REQUIRE(rc != -1, "wave chain: shape not compiled in (dev build)");
   if (rc) return rc;
   VN_CHECK_HIP(hipGetLastError());
   p->last_chain_kernel = 1;

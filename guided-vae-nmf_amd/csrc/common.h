@@ -97,7 +97,10 @@ struct vaenmf_plan {
   // the launch path needs the host once per call instead of once per kernel (a loaded host showed as up to 20 % of
   // idle GPU time between the kernels)
   hipStream_t cap_stream = nullptr;     // capture needs a stream of its own (the caller's may be the null stream)
-  struct EmGraph { std::vector<uint64_t> key; hipGraphExec_t exec; uint64_t used; };
+  struct EmGraph {
+    std::vector<uint64_t> key; hipGraphExec_t exec; uint64_t used;
+    int chain_kernel, w_fused;          // last_chain_kernel / last_w_fused as the captured body left them
+  };
   std::vector<EmGraph> g_cache;         // captured calls, a few signatures (a job alternates batch shapes: 63 / 62 utterances)
   std::vector<std::vector<uint64_t>> g_seen;   // signatures run eagerly once (a signature is captured at its second appearance)
   uint64_t g_tick = 0;
@@ -123,6 +126,18 @@ struct VnChainCall {
   float sd_hi;               // random-walk step of latents 16..31: sd, or 0 when they are padding (latent dimension 16)
   int one_hidden;
 };
+
+// Kernel-choice switches for tests and A/B runs, read from the environment on every call (tests change them inside one
+// process); vaenmf_em_run keys its graphs on them.  plan.hip
+struct VnSwitches {
+  bool wchain4;        // VAENMF_WCHAIN4=0: small batches stay on wchain_kernel instead of wchain4_kernel
+  bool team_chain;     // VAENMF_TEAM_CHAIN=1: the team kernel of engine.hip for every shape
+  bool wfused;         // VAENMF_WFUSED=0: W statistics + W update as two kernels
+  bool wgroup;         // VAENMF_WGROUP=0: small batches stay on wstats_fused_kernel instead of wstats_group_kernel
+  int wfused_grid;     // VAENMF_WFUSED_GRID=n: at most n workgroups for wstats_fused_kernel (0: no cap)
+  bool keep_zs;        // VAENMF_KEEP_ZS=1: the E-step chains of the sample-store path record their samples anyway
+};
+VnSwitches vn_switches();
 
 enum { VN_K_CHAIN = 0, VN_K_WSTATS = 1, VN_K_WUPDATE = 2, VN_K_HG = 3, VN_K_WF = 4, VN_K_NKINDS = 5 };
 struct ProfScope {   // records a (start, stop) event pair around a launch when profiling is on
@@ -245,26 +260,17 @@ __device__ __forceinline__ Xs128 xs_seed(uint64_t utt_seed, uint32_t frame, uint
   return s;
 }
 // 4 standard normals (two Box-Muller pairs); v_sin/v_cos take revolutions.
-// VN_RNG16 = 1: ONE random word per pair -- radius from its high 16 bits, angle from its low 16 bits -- instead of two
+// ONE random word per pair -- radius from its high 16 bits, angle from its low 16 bits -- instead of two
 // words at 24 bits each: half the generator steps (the proposals are N(0, var_RW) steps of a random walk: a radius on a
 // 2^-16 grid, |eps| <= 4.71 sigma, changes nothing the sampler's distribution can show; any symmetric proposal leaves
 // the Metropolis-Hastings target unchanged).
-#ifndef VN_RNG16
-#define VN_RNG16 1
-#endif
 __device__ __forceinline__ f32x4 normal4(Xs128& st) {
   f32x4 o;
 #pragma unroll
   for (int p = 0; p < 2; ++p) {
-#if VN_RNG16
     const uint32_t a = st.next();
     const float u1 = ((float)(a >> 16) + 1.0f) * 1.52587890625e-5f;  // (0,1], 2^-16 grid
     const float u2 = (float)(a & 0xFFFFu) * 1.52587890625e-5f;       // [0,1)
-#else
-    uint32_t a = st.next(), b = st.next();
-    float u1 = ((float)(a >> 8) + 1.0f) * 5.9604644775390625e-8f;   // (0,1]
-    float u2 = (float)(b >> 8) * 5.9604644775390625e-8f;            // [0,1)
-#endif
     float r = __builtin_amdgcn_sqrtf(-2.0f * fast_log(u1));
     o[2 * p] = r * __builtin_amdgcn_cosf(u2);
     o[2 * p + 1] = r * __builtin_amdgcn_sinf(u2);

@@ -1601,8 +1601,7 @@ static int em_run_body(vaenmf_plan* p, const float* X2, float* W, float* Ht, flo
   // With the sample-variance store on, the M-step never looks at the E-step's latent samples: the wave-private chain kernels
   // then do not record them (Zs = NULL: 123 MB of writes per launch at the bench shape that nothing reads); the Wiener chain
   // below records its own, which is what Zs holds after the reference's run() too (mcem.py:173, :477-482).
-  const char* keep = getenv("VAENMF_KEEP_ZS");          // dev / test switch: 1 = record the E-step samples anyway
-  float* Zs_e = (stored && !(keep && keep[0] == '1') && vn_wchain_supported(p) &&
+  float* Zs_e = (stored && !vn_switches().keep_zs && vn_wchain_supported(p) &&
                  vaenmf_wchain_addressable(p->NT, Rcap, nsE + biE, p->Fs, p->Kp, p->n_utt, 0)) ? nullptr : Zs;
   for (int it = 0; it < niter; ++it) {                  // EM.run, mcem.py:159-165
     rng.call = (uint32_t)it;
@@ -1648,6 +1647,7 @@ extern "C" int vaenmf_em_run(vaenmf_plan* p, const float* X2, float* W, float* H
   auto u64 = [](const void* q) { return (uint64_t)(uintptr_t)q; };
   uint32_t vbits;
   memcpy(&vbits, &var_rw, 4);
+  const VnSwitches sw = vn_switches();                  // kernel choices the captured launches depend on
   uint64_t fo_hash = 1469598103934665603ull;            // the batch's frame offsets (FNV-1a): launches derive grids and chunk tables from them
   for (int32_t v : p->h_frame_off) { fo_hash ^= (uint64_t)(uint32_t)v; fo_hash *= 1099511628211ull; }
   const std::vector<uint64_t> key = {fo_hash,
@@ -1658,16 +1658,20 @@ extern "C" int vaenmf_em_run(vaenmf_plan* p, const float* X2, float* W, float* H
       u64(p->d_wt_utt), u64(p->d_wt_n0), u64(p->d_wt_cnt), u64(p->d_frame_off), u64(p->d_frame_utt), u64(p->d_frame_loc), u64(p->d_tile_utt),
       u64(p->d_tile_n0), u64(p->d_tile_cnt), u64(p->d_utt_seed), u64(p->A1), u64(p->P), u64(p->normW), u64(p->wpart), u64(p->cost_frames), u64(p->w3n), u64(p->w1y), u64(p->b2), u64(p->b3),
       u64(p->wpart64), u64(p->wpart16), u64(p->d_t64_n0), u64(p->d_t64_cnt), u64(p->d_t64_first), u64(p->d_t64_g0), (uint64_t)p->n_t64,
-      (uint64_t)p->cfg.precision, (uint64_t)p->cfg.K, (uint64_t)p->cfg.F};
-  auto after_replay = [&]() {                           // the host-side state an eager call leaves behind
+      (uint64_t)p->cfg.precision, (uint64_t)p->cfg.K, (uint64_t)p->cfg.F,
+      (uint64_t)sw.wchain4, (uint64_t)sw.team_chain, (uint64_t)sw.wfused, (uint64_t)sw.wgroup, (uint64_t)(uint32_t)sw.wfused_grid,
+      (uint64_t)sw.keep_zs};
+  auto after_replay = [&](const vaenmf_plan::EmGraph& gph) {      // the host-side state an eager call leaves behind
     if (stored) { p->store_R = nsWF; p->store_Rs = nsWF + 1; }
+    p->last_chain_kernel = gph.chain_kernel;
+    p->last_w_fused = gph.w_fused;
   };
   constexpr size_t MAX_GRAPHS = 4, MAX_SEEN = 8;
   for (auto& gph : p->g_cache)
     if (gph.key == key) {
       VN_CHECK_HIP(hipGraphLaunch(gph.exec, st));
       gph.used = ++p->g_tick;
-      after_replay();
+      after_replay(gph);
       p->last_em_graph = 1;
       return 0;
     }
@@ -1700,9 +1704,9 @@ extern "C" int vaenmf_em_run(vaenmf_plan* p, const float* X2, float* W, float* H
     (void)hipGraphExecDestroy(p->g_cache[lru].exec);
     p->g_cache.erase(p->g_cache.begin() + lru);
   }
-  p->g_cache.push_back({key, exec, ++p->g_tick});
+  p->g_cache.push_back({key, exec, ++p->g_tick, p->last_chain_kernel, p->last_w_fused});
   VN_CHECK_HIP(hipGraphLaunch(exec, st));
-  after_replay();
+  after_replay(p->g_cache.back());
   p->last_em_graph = 1;
   return 0;
 }

@@ -26,6 +26,18 @@ int vn_ensure_dyn_lds(const void* fn, int bytes) {
   return 0;
 }
 
+VnSwitches vn_switches() {
+  auto env = [](const char* name) { const char* e = getenv(name); return e ? e : ""; };
+  VnSwitches s;
+  s.wchain4 = env("VAENMF_WCHAIN4")[0] != '0';
+  s.team_chain = env("VAENMF_TEAM_CHAIN")[0] == '1';
+  s.wfused = env("VAENMF_WFUSED")[0] != '0';
+  s.wgroup = env("VAENMF_WGROUP")[0] != '0';
+  s.wfused_grid = atoi(env("VAENMF_WFUSED_GRID"));
+  s.keep_zs = env("VAENMF_KEEP_ZS")[0] == '1';
+  return s;
+}
+
 void vaenmf_set_error(const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);

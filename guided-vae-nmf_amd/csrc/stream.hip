@@ -15,63 +15,6 @@
 // Bins of the odd last bin and the padding (f >= Fm: F-1 when F = 16k+1) are handled as one extra
 // element that every lane computes redundantly (same address: a broadcast load).
 #include "common.h"
-#ifndef VN_HG_WAVES
-#define VN_HG_WAVES 4      // minimum waves per SIMD asked of the compiler (register cap 512 / waves)
-#endif
-#ifndef VN_WS_WAVES
-#define VN_WS_WAVES 4
-#endif
-#ifndef VN_ROWCHUNK
-#define VN_ROWCHUNK 1      // rows per uniform branch in RowBatch::for_rows (2, 3, 5 rows per branch spill more at the 128-register cap: 87 / 106 / 275 scratch operations against 50)
-#endif
-#ifndef VN_ROT
-#define VN_ROT 1          // rotating-register W-statistics / H,g kernels for the bench shapes (dev builds: 0 = the batch forms)
-#endif
-#ifndef VN_WS_EXACT
-#define VN_WS_EXACT 0     // exact-sample-count instantiations of wstats_stream2 (R = 30 / 10)
-#endif
-#ifndef VN_HG_FULL2
-#define VN_HG_FULL2 1
-#endif
-#ifndef VN_HG_FULLF
-#define VN_HG_FULLF 1
-#endif
-#ifndef VN_HG_FULL2_KMAX
-#define VN_HG_FULL2_KMAX 16     // (rank 32: the whole-frame batch still spills, 288 bytes, and gains nothing)
-#endif
-#ifndef VN_HG_EXACT
-#define VN_HG_EXACT 1     // exact-sample-count instantiations of hg_stream (R = 30 / 10, one chunk, rank <= 8): no per-row branches, rows consumed
-                          // as they arrive (precise vmcnt counts): 0.198 -> 0.172 ms.  (Slower while the extra-bin addresses still spilled.)
-#endif
-#ifndef VN_HG_STAGGER
-#define VN_HG_STAGGER 0     // s_sleep(127) units (8128 cycles each) per hardware wave slot at the start of hg_stream
-#endif
-#ifndef VN_HG_PROBE
-#define VN_HG_PROBE 0     // dev probes of hg_stream: 1 = rows loaded, arithmetic reduced to one add per element; 2 = every row read from the same cached address
-#endif
-#ifndef VN_HG_REPACK
-#define VN_HG_REPACK 1
-#endif
-#ifndef VN_ROWGRP
-#define VN_ROWGRP 6     // rows whose arithmetic the scheduler may interleave in the exact-count stream kernels
-#endif
-#ifndef VN_HG_EXACT2
-#define VN_HG_EXACT2 1     // exact-count H/g kernel for two-chunk rows at rank <= 16 (F = 513, K = 10: 0.2625 -> 0.250 ms)
-#endif
-// Non-temporal loads for the sample-variance rows (each row is read once per kernel and the store, 0.54 GB, passes every
-// cache): measured on one box, alternating builds -- W statistics 0.131-0.137 -> 0.121-0.124 ms, step 71.9 -> 70.5 ms (the H/g
-// kernel, VALU-bound, does not move).  What the rows compete with is the chain's own write-back: with non-temporal STORES in
-// the chain the W statistics drop to 0.099 ms (4.9 TB/s), but the chain pays 0.39 -> 0.53 ms for them (sc1 stores: 0.46), so
-// the stores stay cached.
-#ifndef VN_ROW_AUX
-#define VN_ROW_AUX 2     // cache policy of the row loads of wstats_rot / wstats_fused (buffer loads: 2 = nt)
-#endif
-#ifndef VN_ROW_NT
-#define VN_ROW_NT 1      // non-temporal row loads in the RowBatch kernels (wstats_stream, wstats_group, hg_stream, wf_stream)
-#endif
-#ifndef VN_STREAM2
-#define VN_STREAM2 1      // frame-pipelined W-statistics kernel (dev builds: 0 = the batch-at-a-time form)
-#endif
 
 int vn_ensure_dyn_lds(const void* fn, int bytes);     // plan.hip
 
@@ -79,6 +22,15 @@ namespace {
 
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
+
+constexpr int ST_WAVES = 4;      // minimum waves per SIMD asked of the compiler (register cap 512 / waves), rank <= 8, one chunk
+// Non-temporal loads for the sample-variance rows (each row is read once per kernel and the store, 0.54 GB, passes every
+// cache): measured on one box, alternating builds -- W statistics 0.131-0.137 -> 0.121-0.124 ms, step 71.9 -> 70.5 ms (the H/g
+// kernel, VALU-bound, does not move).  What the rows compete with is the chain's own write-back: with non-temporal STORES in
+// the chain the W statistics drop to 0.099 ms (4.9 TB/s), but the chain pays 0.39 -> 0.53 ms for them (sc1 stores: 0.46), so
+// the stores stay cached.  The RowBatch kernels load rows with __builtin_nontemporal_load, wstats_fused through a buffer
+// resource with this cache policy:
+constexpr int ROW_AUX = 2;       // (buffer loads: 2 = nt)
 
 struct StreamArgs {
   const void* VsS;             // [NT][Rs][Fs], float or bf16 (template ST)
@@ -345,13 +297,9 @@ struct RowBatch {
 #pragma unroll
     for (int r = 0; r < RB; ++r)
       if (r == 0 || on(r)) {
-#if VN_HG_PROBE == 2
-        const ST* row = reinterpret_cast<const ST*>(fc.a.VsS) + (size_t)(__builtin_amdgcn_readlane(sl, r) & 1) * fc.a.Fs;
-#else
         const ST* row = base + (size_t)__builtin_amdgcn_readlane(sl, r) * fc.a.Fs;
-#endif
 #pragma unroll
-        for (int c = 0; c < NCH; ++c) raw[r][c] = VN_ROW_NT ? __builtin_nontemporal_load(reinterpret_cast<const raw_t*>(row + fc.fo[c])) : *reinterpret_cast<const raw_t*>(row + fc.fo[c]);
+        for (int c = 0; c < NCH; ++c) raw[r][c] = __builtin_nontemporal_load(reinterpret_cast<const raw_t*>(row + fc.fo[c]));
       }
     // extra bin, raw bits (x() converts at the use: a conversion here would wait for every load above)
     if (fc.has_x) {
@@ -394,7 +342,8 @@ struct RowBatch {
   // region and a precise vmcnt count); only the last, partial chunk checks row by row.
   template <typename FN>
   __device__ __forceinline__ void for_rows(FN f) const {
-    constexpr int CH = VN_ROWCHUNK;
+    // (2, 3, 5 rows per branch spill more at the 128-register cap: 87 / 106 / 275 scratch operations against 50)
+    constexpr int CH = 1;
 #pragma unroll
     for (int r0 = 0; r0 < RB; r0 += CH) {
       if (RT > 0 ? r0 + CH <= RT : r0 + CH <= nr) {
@@ -440,7 +389,7 @@ __device__ __forceinline__ void wave_frames(int NT, int& n_beg, int& n_end) {
 }
 
 template <int NCH, int KP, typename ST>
-__global__ __launch_bounds__(256, (KP <= 8 && NCH == 1) ? VN_WS_WAVES : 2) void wstats_stream_kernel(const StreamArgs a) {
+__global__ __launch_bounds__(256, (KP <= 8 && NCH == 1) ? ST_WAVES : 2) void wstats_stream_kernel(const StreamArgs a) {
   extern __shared__ __attribute__((aligned(16))) float wlds[];
   FrameCtx<NCH, KP, ST> fc(a, wlds + (KP <= 8 ? (size_t)(threadIdx.x >> 6) * a.Fs * KP : 0));
   fc.stage_block_w();
@@ -560,25 +509,17 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1) ? VN_WS_WAVES : 2) void 
 
 // RT > 0: exactly RT samples per frame (no per-row branch: 90 uniform branches per frame otherwise)
 template <int NCH, int KP, typename ST, int RT = 0>
-__global__ __launch_bounds__(256, (KP <= 8 && NCH == 1 && !(VN_HG_FULLF && sizeof(ST) == 4)) ? VN_HG_WAVES : 2) void hg_stream_kernel(const StreamArgs a) {
+__global__ __launch_bounds__(256, (KP <= 8 && NCH == 1 && sizeof(ST) == 2) ? ST_WAVES : 2) void hg_stream_kernel(const StreamArgs a) {
   extern __shared__ __attribute__((aligned(16))) float wlds[];
   FrameCtx<NCH, KP, ST> fc(a, wlds + (KP <= 8 ? (size_t)(threadIdx.x >> 6) * a.Fs * KP : 0));
   fc.stage_block_w();
-  // (two chunks, rank <= 16: 0.306 -> 0.286 ms on the 1024-pt shape; at rank 32 the registers do not suffice: 0.535 -> 0.608)
+  // (two chunks, rank <= 16: 0.306 -> 0.286 ms on the 1024-pt shape; at rank 32 the registers do not suffice: 0.535 -> 0.608,
+  // and the whole-frame batch still spills, 288 bytes, and gains nothing)
   // float rows (bf16x3 mode), one chunk: 32 rows x 4 registers at two wavefronts per SIMD hold the whole frame as well (16 per
   // batch re-read both batches in every pass: 3x the traffic of a kernel that is memory-bound with float rows)
-  using RBt = RowBatch<NCH, ST, 1, RT, ((VN_HG_FULL2 && sizeof(ST) == 2 && NCH == 2 && KP <= VN_HG_FULL2_KMAX) || (VN_HG_FULLF && sizeof(ST) == 4 && NCH == 1 && KP <= 8)) ? 32 : 0>;
+  using RBt = RowBatch<NCH, ST, 1, RT, ((sizeof(ST) == 2 && NCH == 2 && KP <= 16) || (sizeof(ST) == 4 && NCH == 1 && KP <= 8)) ? 32 : 0>;
   int n_beg, n_end;
   wave_frames(a.NT, n_beg, n_end);
-#if VN_HG_STAGGER > 0
-  {
-    // The wavefronts of a SIMD start together and do the same work per frame, so they would all load, then all
-    // compute, in convoy (T = T_mem + T_compute).  Stagger them by their hardware wave slot: slot i waits i quarter
-    // periods once, and the load phase of one then falls under the arithmetic of the others for the rest of the launch.
-    const unsigned slot = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | ((4 - 1) << 11)) & 3u;     // HW_REG_HW_ID, wave_id[3:0]
-    for (unsigned k = 0; k < slot * VN_HG_STAGGER; ++k) __builtin_amdgcn_s_sleep(127);
-  }
-#endif
   const bool one = a.R <= RBt::RB;                    // the frame fits one batch: its rows are read once
   for (int n = n_beg; n < n_end; ++n) {
     const ST* base = reinterpret_cast<const ST*>(a.VsS) + (size_t)n * a.Rs * a.Fs;
@@ -624,11 +565,6 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1 && !(VN_HG_FULLF && sizeo
         auto row1 = [&](int r) {
           f32x4 v[NCH];
           rb.get(r, v);
-#if VN_HG_PROBE == 1
-#pragma unroll
-          for (int c = 0; c < NCH; ++c) { a1[c] += v[c]; a2[c] += v[c]; }
-          return;
-#endif
 #pragma unroll
           for (int c = 0; c < NCH; ++c) {
             // two bins per instruction (v_pk_fma / v_pk_add_f32: next to transcendentals a packed instruction costs the
@@ -671,7 +607,7 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1 && !(VN_HG_FULLF && sizeo
     }
     // ---- g update (mcem.py:138-142 / :564-568)
     float nu = 0.f, de = 0.f;
-    if (one && VN_HG_REPACK) rb.repack();      // (no unpacked floats carried from pass to pass: see RowBatch::repack)
+    if (one) rb.repack();      // (no unpacked floats carried from pass to pass: see RowBatch::repack)
     {
       f32x4 ng[NCH], dg[NCH];
       float ngx = 0.f, dgx = 0.f;
@@ -682,11 +618,6 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1 && !(VN_HG_FULLF && sizeo
         auto row2 = [&](int r) {
           f32x4 v[NCH];
           rb.get(r, v);
-#if VN_HG_PROBE == 1
-#pragma unroll
-          for (int c = 0; c < NCH; ++c) { dg[c] += v[c]; ng[c] += v[c]; }
-          return;
-#endif
 #pragma unroll
           for (int c = 0; c < NCH; ++c) {
             const f32x2 q0 = rcp2(gn2 * v[c].lo + vb[c].lo), q1 = rcp2(gn2 * v[c].hi + vb[c].hi);
@@ -713,7 +644,7 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1 && !(VN_HG_FULLF && sizeo
     const float gnew = gn * __builtin_amdgcn_sqrtf(nu * fast_rcp(de));                     // mcem.py:142
     if (fc.lane == 0) a.g[n] = gnew;
     const f32x2 gw2 = {gnew, gnew};
-    if (one && VN_HG_REPACK) rb.repack();
+    if (one) rb.repack();
     // ---- cost (mcem.py:70) with the refreshed variances (:151-152); samples two at a time:
     // log Vx0 + log Vx1 = log(Vx0 Vx1), 1/Vx0 + 1/Vx1 = (Vx0 + Vx1)/(Vx0 Vx1)
     f32x4 cl[NCH], cx[NCH];
@@ -724,7 +655,6 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1 && !(VN_HG_FULLF && sizeo
       if (!one) rb.load(fc, base, srow, r0, a.R);
 #pragma unroll
       for (int r = 0; r < RBt::RB; r += 2) {
-        if (VN_HG_PROBE == 1) continue;
         if (rb.on(r + 1)) {
           f32x4 v0[NCH], v1[NCH];
           rb.get(r, v0);
@@ -766,7 +696,7 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1 && !(VN_HG_FULLF && sizeo
 }
 
 template <int NCH, int KP, typename ST>
-__global__ __launch_bounds__(256, (KP <= 8 && NCH == 1) ? VN_WS_WAVES : 2) void wf_stream_kernel(const StreamArgs a) {
+__global__ __launch_bounds__(256, (KP <= 8 && NCH == 1) ? ST_WAVES : 2) void wf_stream_kernel(const StreamArgs a) {
   extern __shared__ __attribute__((aligned(16))) float wlds[];
   FrameCtx<NCH, KP, ST> fc(a, wlds + (KP <= 8 ? (size_t)(threadIdx.x >> 6) * a.Fs * KP : 0));
   fc.stage_block_w();
@@ -901,7 +831,8 @@ __global__ __launch_bounds__(256, 2) void wstats_stream2_kernel(const StreamArgs
     for (int c = 0; c < NCH; ++c) a1[c] = a2[c] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int r = 0; r < RBt::RB; ++r) {
-      if (RT > 0 && (r % VN_ROWGRP) == 0) __builtin_amdgcn_sched_barrier(0);     // bound the interleave (registers)
+      constexpr int ROWGRP = 6;      // rows whose arithmetic the scheduler may interleave in the exact-count form
+      if (RT > 0 && (r % ROWGRP) == 0) __builtin_amdgcn_sched_barrier(0);     // bound the interleave (registers)
       if (rb.on(r)) {
         f32x4 v[NCH];
         rb.get(r, v);
@@ -943,7 +874,7 @@ __global__ __launch_bounds__(256, 2) void wstats_stream2_kernel(const StreamArgs
 
 
 // ============================================================================
-// Rotating-register forms (bf16 rows, one 256-bin chunk, rank <= 8, exactly RT samples per frame): the bench shapes.
+// Rotating registers (bf16 rows, one 256-bin chunk, rank <= 8, exactly RT samples per frame): the bench shapes.
 // A wavefront keeps ONE frame's rows in registers (2 per row) and refills each row's registers with the same row of
 // the NEXT frame right after its last use, so RT row loads stay in flight per wavefront all the time and the loop is
 // straight-line: the compiler's vmcnt counts are exact (wait for the oldest row only), which no form with per-row
@@ -1011,7 +942,7 @@ struct RotCtx {
     const unsigned so = (unsigned)n * frameb + (unsigned)__builtin_amdgcn_readlane(sl, r) * rowb;
     unsigned vo = vbase;
     asm volatile("" : "+v"(vo) : "v"(after));
-    raw[S][r] = __builtin_bit_cast(bf16x4, __builtin_amdgcn_raw_buffer_load_b64(vrs, vo, so, VN_ROW_AUX));
+    raw[S][r] = __builtin_bit_cast(bf16x4, __builtin_amdgcn_raw_buffer_load_b64(vrs, vo, so, ROW_AUX));
   }
   template <int S>
   __device__ __forceinline__ void req_x(int n, int sl, bool on) {
@@ -1032,83 +963,13 @@ __device__ __forceinline__ void rot_h(float hl, float (&h)[KP]) {
   for (int k = 0; k < KP; ++k) h[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, hl), k));
 }
 
-template <int KP, int RT>
-__global__ __launch_bounds__(256, 2) void wstats_rot_kernel(const StreamArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float wlds[];
-  FrameCtx<1, KP, __bf16> fc(a, wlds + (size_t)(threadIdx.x >> 6) * a.Fs * KP);
-  int n_beg, n_end;
-  wave_frames(a.NT, n_beg, n_end);
-  if (n_beg >= n_end) return;
-  RotCtx<KP, RT> rc(a, fc);
-  // Small operands TWO frames ahead (cur, nx1, nx2), like the slot map: requested a single frame ahead they are younger
-  // than the previous step's refills, and the wait for them (vmcnt counts in order) at the top of a step would be a wait
-  // for every row of the frame -- the rows refilled last would get no time at all.
-  RotSmall<KP> cur, nx1, nx2;
-  int sl[2];                   // sl[S]: slots of the frame that goes into set S next
-  const int n_last = n_end - 1;
-  auto clampf = [&](int n) { return n < n_last ? n : n_last; };
-  {
-    sl[0] = rc.slots(n_beg);
-    rc.req_small(n_beg, cur);
-    rc.req_small(clampf(n_beg + 1), nx1);
-    sl[1] = rc.slots(clampf(n_beg + 1));
-#pragma unroll
-    for (int r = 0; r < RT; ++r) rc.template req_row<0>(n_beg, sl[0], r, 0.f, rc.voff);
-    rc.template req_x<0>(n_beg, sl[0], true);
-  }
-  // frame n from set S; set 1-S gets frame n+1 (nothing behind the last frame: refills past the buffer's end)
-  auto step = [&](int n, auto set_c) {
-    constexpr int S = decltype(set_c)::value, T = 1 - S;
-    const bool more = n < n_last;
-    const int nn = clampf(n + 1);
-    rc.req_small(clampf(n + 2), nx2);
-    sl[S] = rc.slots(clampf(n + 2));
-    const int utt = cur.utt();
-    const float gn = cur.g();
-    fc.set_utt(utt);
-    float h[KP];
-    rot_h<KP>(cur.pk, h);
-    f32x4 vb[1], a1, a2;
-    float vbx;
-    fc.noise_var(utt, h, vb, vbx);
-    a1 = a2 = f32x4{0.f, 0.f, 0.f, 0.f};
-    const f32x2 g2 = {gn, gn};
-    const unsigned vnext = more ? rc.voff : 0xF0000000u;
-#pragma unroll
-    for (int r = 0; r < RT; ++r) {
-      const f32x4 v = rc.template row<S>(r);
-      const f32x2 q0 = rcp2(g2 * v.lo + vb[0].lo), q1 = rcp2(g2 * v.hi + vb[0].hi);
-      a1.lo += q0; a1.hi += q1;
-      a2.lo = q0 * q0 + a2.lo; a2.hi = q1 * q1 + a2.hi;
-      rc.template req_row<T>(nn, sl[T], r, a2[3], vnext);
-      __builtin_amdgcn_sched_barrier(0);             // one row per region
-    }
-    const float q = fast_rcp(gn * rc.template x<S>() + vbx) * rc.xmask();
-    rc.template req_x<T>(nn, sl[T], more);
-    const float a1x = wave_sum(q), a2x = wave_sum(q * q);
-    a2 *= cur.x2;
-    f32x4 o1[1] = {a1}, o2[1] = {a2};
-    fc.store_row(a.A1 + (size_t)n * a.Fs, o1, a1x);
-    fc.store_row(a.P + (size_t)n * a.Fs, o2, a2x * cur.x2x());
-    cur = nx1;
-    nx1 = nx2;
-  };
-  int n = n_beg;
-  for (; n < n_last; n += 2) {
-    step(n, std::integral_constant<int, 0>{});
-    step(n + 1, std::integral_constant<int, 1>{});
-  }
-  if (n == n_last) step(n, std::integral_constant<int, 0>{});
-}
-
-
 // ----------------------------------------------------------------------------
-// W statistics AND the W update's sums over frames in one pass (mcem.py:107-110): wstats_rot's frame loop, but the
+// W statistics AND the W update's sums over frames in one pass (mcem.py:107-110): a rotating-register frame loop whose
 // frame's A1 = sum_r 1/Vx and P = X2 sum_r 1/Vx^2 never leave the registers -- each wavefront adds P[f] H[k, n] and
 // A1[f] H[k, n] of its frames to 2 x 4 bins x KP accumulators per lane (the extra bin F-1: lane k keeps rank k), the four
 // wavefronts of a workgroup (one tile of <= 64 consecutive frames of ONE utterance, 16 per wavefront) add theirs up
 // through LDS in fixed order, and the workgroup writes one partial sum [Fs][2 KP] per tile.  w_update_tiles_kernel
-// (aux.hip) adds an utterance's tiles in fixed order.  Against wstats_rot + w_partial: no A1 / P round trip through
+// (aux.hip) adds an utterance's tiles in fixed order.  Against W statistics + w_partial: no A1 / P round trip through
 // HBM (2 x NT x Fs floats written and read back) and one launch less per EM iteration; sums in a fixed order, so
 // results are reproducible run to run.
 // ----------------------------------------------------------------------------
@@ -1116,7 +977,7 @@ constexpr int WF_TILE = 64, WF_WFR = 16;            // frames per workgroup tile
 // LDS of a workgroup: W of the tile's utterance, rank-major [KP][Fs] (shared by the four wavefronts: they are in one
 // utterance by construction), then per wavefront 2 KP accumulator rows [slot = 2 k + stat][lane][4 bins] (a lane reads and
 // writes its 16 bytes of a slot: conflict-free ds_read/write_b128) and 2 x 64 floats for the extra bin.  The accumulators
-// live in LDS, not in registers: wstats_rot's two register sets of rows leave no room for 64 more (it spilled 175).
+// live in LDS, not in registers: the two register sets of rows leave no room for 64 more (it spilled 175).
 template <int KP>
 __host__ __device__ constexpr int wf_acc_floats() { return 2 * KP * 256 + 128; }
 template <int KP, int RT>
@@ -1391,65 +1252,40 @@ int launch_st(StreamArgs a, int grid, hipStream_t st) {
   const size_t one = (size_t)a.Fs * KP * sizeof(float);
   const size_t lds = KP <= 8 ? 4 * one : (one <= 72 * 1024 ? one : 0);
   a.w_blk_lds = KP > 8 && lds > 0;
-  const void* fn = KIND == SK_WSTATS ? (const void*)wstats_stream_kernel<NCH, KP, ST>
-                   : (KIND == SK_HG ? (const void*)hg_stream_kernel<NCH, KP, ST> : (const void*)wf_stream_kernel<NCH, KP, ST>);
-  if (int e = vn_ensure_dyn_lds(fn, 80 * 1024)) return e;
-  constexpr bool PIPE_OK = NCH == 1 && KP <= 8;
-  // (The same form of the H/g kernel needs two register sets of 60 plus the three passes' working set: it spills at 256
-  // registers with 30 samples -- 0.62 ms against 0.17 for the batch form -- and gains nothing with 10; not kept.)
-  if (VN_ROT && PIPE_OK && sizeof(ST) == 2 && KIND == SK_WSTATS && (a.R == 30 || a.R == 10)) {
-    constexpr int K1 = PIPE_OK ? KP : 8;
-    int g4 = a.n_sms * 2;                               // one resident set: 2 workgroups of 4 wavefronts per CU (two per SIMD)
-    if (g4 * 4 > a.NT) g4 = (a.NT + 3) / 4;
-    if (a.R == 30) {
-      if (int e = vn_ensure_dyn_lds((const void*)wstats_rot_kernel<K1, 30>, 80 * 1024)) return e;
-      hipLaunchKernelGGL((wstats_rot_kernel<K1, 30>), dim3(g4), dim3(256), lds, st, a);
-    } else {
-      if (int e = vn_ensure_dyn_lds((const void*)wstats_rot_kernel<K1, 10>, 80 * 1024)) return e;
-      hipLaunchKernelGGL((wstats_rot_kernel<K1, 10>), dim3(g4), dim3(256), lds, st, a);
+  auto go = [&](auto* fn, int g) -> int {
+    if (int e = vn_ensure_dyn_lds((const void*)fn, 80 * 1024)) return e;
+    hipLaunchKernelGGL(fn, dim3(g), dim3(256), lds, st, a);
+    return 0;
+  };
+  if constexpr (KIND == SK_WSTATS) {
+    if constexpr (NCH == 1 && KP <= 8) {
+      if (a.R <= RowBatch<NCH, ST>::RB) {
+        // frame-pipelined form: two resident wavefronts per SIMD, one resident set per launch.  (The same form of the H/g
+        // kernel was measured twice, 0.23 ms against 0.17-0.20 for the batch-at-a-time one at four wavefronts per SIMD,
+        // and is not kept; exact-row-count instantiations of this one spill: 0.29 vs 0.155 ms.)
+        int g2 = a.n_sms * 2;
+        if (g2 * 4 > a.NT) g2 = (a.NT + 3) / 4;
+        return go(wstats_stream2_kernel<NCH, KP, ST, 0>, g2);
+      }
     }
-    return 0;
+    return go(wstats_stream_kernel<NCH, KP, ST>, grid);
+  } else if constexpr (KIND == SK_HG) {
+    if constexpr (NCH == 1 && KP <= 8) {
+      // exact-sample-count instantiations (one chunk, rank <= 8): no per-row branches, rows consumed as they arrive (precise
+      // vmcnt counts): 0.198 -> 0.172 ms.  (Slower while the extra-bin addresses still spilled.)  (The rotating-register form
+      // needs two register sets of 60 plus the three passes' working set: it spills at 256 registers with 30 samples --
+      // 0.62 ms against 0.17 for the batch form -- and gains nothing with 10; not kept.)
+      if (a.R == 30) return go(hg_stream_kernel<NCH, KP, ST, 30>, grid);
+      if (a.R == 10) return go(hg_stream_kernel<NCH, KP, ST, 10>, grid);
+    } else if constexpr (NCH == 2 && sizeof(ST) == 2 && KP == 16) {
+      // two 256-bin chunks (F = 513), rank 16, bf16 rows: the whole 30-sample frame sits in one batch of registers
+      // (RBX = 32): the exact-count form drops the per-row branches here as well (F = 513, K = 10: 0.2625 -> 0.250 ms)
+      if (a.R == 30) return go(hg_stream_kernel<NCH, KP, ST, 30>, grid);
+    }
+    return go(hg_stream_kernel<NCH, KP, ST>, grid);
+  } else {
+    return go(wf_stream_kernel<NCH, KP, ST>, grid);
   }
-  if (PIPE_OK && VN_STREAM2 && KIND == SK_WSTATS && a.R <= RowBatch<NCH, ST>::RB) {
-    // frame-pipelined form: two resident wavefronts per SIMD, one resident set per launch.  (The same form of the H/g
-    // kernel was measured twice, 0.23 ms against 0.17-0.20 for the batch-at-a-time one at four wavefronts per SIMD,
-    // and is not kept; exact-row-count instantiations of this one spill: 0.29 vs 0.155 ms.)
-    int g2 = a.n_sms * 2;
-    if (g2 * 4 > a.NT) g2 = (a.NT + 3) / 4;
-    constexpr int N1 = PIPE_OK ? NCH : 1, K1 = PIPE_OK ? KP : 8;
-#define VN_GO2(RT)                                                                                         \
-    do {                                                                                                       \
-      if (int e = vn_ensure_dyn_lds((const void*)wstats_stream2_kernel<N1, K1, ST, RT>, 80 * 1024)) return e; \
-      hipLaunchKernelGGL((wstats_stream2_kernel<N1, K1, ST, RT>), dim3(g2), dim3(256), lds, st, a);           \
-    } while (0)
-    constexpr int RBm = RowBatch<N1, ST>::RB;
-    if (VN_WS_EXACT && a.R == 30 && RBm >= 30) VN_GO2((RBm >= 30 ? 30 : 0));
-    else if (VN_WS_EXACT && a.R == 10) VN_GO2(10);
-    else VN_GO2(0);
-#undef VN_GO2
-    return 0;
-  }
-  if (KIND == SK_WSTATS) hipLaunchKernelGGL((wstats_stream_kernel<NCH, KP, ST>), dim3(grid), dim3(256), lds, st, a);
-  else if (KIND == SK_HG) {
-    constexpr int RBm = (VN_HG_FULLF && sizeof(ST) == 4 && NCH == 1 && KP <= 8) ? 32 : RowBatch<NCH, ST>::RB;     // (as hg_stream_kernel's RBt)
-    if (VN_HG_EXACT && NCH == 1 && KP <= 8 && a.R == 30 && RBm >= 30) {
-      if (int e = vn_ensure_dyn_lds((const void*)hg_stream_kernel<NCH, KP, ST, (RBm >= 30 && NCH == 1 ? 30 : 0)>, 80 * 1024)) return e;
-      hipLaunchKernelGGL((hg_stream_kernel<NCH, KP, ST, (RBm >= 30 && NCH == 1 ? 30 : 0)>), dim3(grid), dim3(256), lds, st, a);
-    } else if (VN_HG_EXACT && NCH == 1 && KP <= 8 && a.R == 10) {
-      if (int e = vn_ensure_dyn_lds((const void*)hg_stream_kernel<NCH, KP, ST, (RBm >= 10 && NCH == 1 ? 10 : 0)>, 80 * 1024)) return e;
-      hipLaunchKernelGGL((hg_stream_kernel<NCH, KP, ST, (RBm >= 10 && NCH == 1 ? 10 : 0)>), dim3(grid), dim3(256), lds, st, a);
-#if VN_HG_EXACT2
-    } else if (NCH == 2 && sizeof(ST) == 2 && KP == 16 && a.R == 30) {
-      // two 256-bin chunks (F = 513), rank <= 16, bf16 rows: the whole 30-sample frame sits in one batch of registers
-      // (RBX = 32): the exact-count form drops the per-row branches here as well
-      constexpr int RT2 = (NCH == 2 && sizeof(ST) == 2 && KP == 16) ? 30 : 0;
-      if (int e = vn_ensure_dyn_lds((const void*)hg_stream_kernel<NCH, KP, ST, RT2>, 80 * 1024)) return e;
-      hipLaunchKernelGGL((hg_stream_kernel<NCH, KP, ST, RT2>), dim3(grid), dim3(256), lds, st, a);
-#endif
-    } else hipLaunchKernelGGL((hg_stream_kernel<NCH, KP, ST>), dim3(grid), dim3(256), lds, st, a);
-  }
-  else hipLaunchKernelGGL((wf_stream_kernel<NCH, KP, ST>), dim3(grid), dim3(256), lds, st, a);
-  return 0;
 }
 template <int KIND, int NCH, int KP>
 int launch_one(const StreamArgs& a, int grid, hipStream_t st) {
@@ -1495,18 +1331,14 @@ int vn_launch_w_update(const vaenmf_plan* p, float* W, const float* Ht, hipStrea
 int vn_launch_w_update_tiles(const vaenmf_plan* p, float* W, hipStream_t st, bool groups);
 
 namespace {
-// W statistics + the W update's sums in one kernel: the bench shapes of wstats_rot (bf16 rows, one 256-bin chunk, rank <= 8,
+// W statistics + the W update's sums in one kernel: the bench shapes (bf16 rows, one 256-bin chunk, rank <= 8,
 // 30 or 10 samples per frame, NMF noise model).  VAENMF_WFUSED=0 keeps the two-kernel path (A/B runs, tests).
 bool w_fused_ok(const vaenmf_plan* p, const StreamArgs& a) {
-  if (!(VN_ROT && !a.store_f32 && p->Kp == 8 && (p->Fm + 255) / 256 == 1 && (a.R == 30 || a.R == 10) && !a.gains_only)) return false;
-  const char* e = getenv("VAENMF_WFUSED");              // (read per call: tests switch it inside one process)
-  return !(e && e[0] == '0');
+  return !a.store_f32 && p->Kp == 8 && (p->Fm + 255) / 256 == 1 && (a.R == 30 || a.R == 10) && !a.gains_only && vn_switches().wfused;
 }
 // small batches: one workgroup per 16-frame group (VAENMF_WGROUP=0 keeps the tile kernel: tests)
 bool w_group_ok(const vaenmf_plan* p) {
-  if (!(p->wpart16 && p->n_wtiles <= p->n_sms)) return false;
-  const char* e = getenv("VAENMF_WGROUP");
-  return !(e && e[0] == '0');
+  return p->wpart16 && p->n_wtiles <= p->n_sms && vn_switches().wgroup;
 }
 int launch_w_group(const vaenmf_plan* p, StreamArgs a, hipStream_t st) {
   const size_t lds = ((size_t)a.Fs * 8 + (size_t)wf_acc_floats<8>()) * sizeof(float);
@@ -1520,10 +1352,8 @@ int launch_w_fused(const vaenmf_plan* p, StreamArgs a, hipStream_t st) {
   a.t64_n0 = p->d_t64_n0; a.t64_cnt = p->d_t64_cnt; a.n_t64 = p->n_t64; a.wpart64 = p->wpart64;
   const size_t lds = ((size_t)a.Fs * 8 + (size_t)4 * wf_acc_floats<8>()) * sizeof(float);
   int grid = a.n_sms * 2;                               // one resident set: 2 workgroups of 4 wavefronts per CU
-  if (const char* e = getenv("VAENMF_WFUSED_GRID")) {   // (tests: a small grid makes every workgroup walk several tiles / utterances)
-    const int g = atoi(e);
-    if (g > 0 && g < grid) grid = g;
-  }
+  const int g = vn_switches().wfused_grid;              // (tests: a small grid makes every workgroup walk several tiles / utterances)
+  if (g > 0 && g < grid) grid = g;
   if (grid > p->n_t64) grid = p->n_t64;
   if (a.R == 30) {
     if (int e = vn_ensure_dyn_lds((const void*)wstats_fused_kernel<8, 30>, 80 * 1024)) return e;

@@ -781,6 +781,63 @@ def test_em_run_graph_replay_equals_launch_by_launch(prec):
     assert np.array_equal(resB[1], resB[0]) and np.array_equal(resB[2], resB[0])
 
 
+def test_em_run_graph_honours_the_kernel_switches():
+    """A replayed vaenmf_em_run graph reports the kernels its captured body chose (VAENMF_Q_CHAIN_KERNEL,
+    VAENMF_Q_W_FUSED), and the kernel-choice switches are part of the graph's signature: with VAENMF_WFUSED=0 set on a
+    plan that holds a graph of the same call, the call runs the two-kernel W statistics instead of replaying the old graph.
+    One engine with fixed buffers, two batches: more 16-frame wave tiles than CUs (wchain_kernel, wstats_fused_kernel) and
+    one utterance (wchain4_kernel, wstats_group_kernel); then the two signatures alternate on the same plan."""
+    need_gpu()
+    from vaenmf import _lib
+    F, K, R = 257, 8, 10
+    n_sms = torch.cuda.get_device_properties(0).multi_processor_count
+    params = orc.xavier_normal_params([F, 32, [128, 128]], seed=5, bias_std=0.05)
+    g = np.random.default_rng(7)
+    large = [1024] * (n_sms // 64 + 1)                   # 64 wave tiles per utterance
+    small = [100]
+    inputs = {}
+    for counts in (large, small):
+        Xs = [((g.standard_normal((n, F)) + 1j * g.standard_normal((n, F))) * (0.5 + 3 * np.exp(-np.arange(F) / 60.0))).astype(np.complex64) for n in counts]
+        W0 = [np.maximum(g.random((F, K)), 1e-8).astype(np.float32) for _ in counts]
+        H0 = [np.maximum(g.random((K, n)), 1e-8).astype(np.float32) for n in counts]
+        inputs[len(counts)] = (counts, Xs, W0, H0)
+    query = lambda eng, q: _lib.lib().vaenmf_plan_query(eng._plan, q)
+
+    def call(eng, counts):
+        _, Xs, W0, H0 = inputs[len(counts)]
+        eng.bind(counts, Rcap=R, seeds=list(range(len(counts))))
+        eng.set_spectrogram(Xs)
+        eng.init_nmf(W0, H0)
+        cost, s, _ = eng.run(2, R, 3, R, 3, 0.01)
+        out = (cost.cpu().numpy(), s.cpu().numpy())
+        return out, query(eng, _lib.Q_EM_GRAPH), query(eng, _lib.Q_CHAIN_KERNEL), query(eng, _lib.Q_W_FUSED)
+
+    eng = make_engine(params, F, K, large, Rcap=R, precision="bf16")
+    kernels = {}
+    for counts, chain_k, w_k in ((large, 1, 1), (small, 2, 2)):
+        runs = [call(eng, counts) for _ in range(3)]     # eager, capture, replay
+        assert [r[1] for r in runs] == [0, 1, 1]
+        assert runs[0][2:] == (chain_k, w_k) and runs[2][2:] == runs[0][2:], [r[2:] for r in runs]
+        for r in runs[1:]:
+            assert np.array_equal(r[0][0], runs[0][0][0]) and np.array_equal(r[0][1], runs[0][0][1])
+        kernels[len(counts)] = runs[2][2:]
+        os.environ["VAENMF_WFUSED"] = "0"
+        try:
+            off = [call(eng, counts) for _ in range(3)]  # a signature of its own: eager, capture, replay
+            ref = call(make_engine(params, F, K, counts, Rcap=R, precision="bf16"), counts)
+        finally:
+            os.environ.pop("VAENMF_WFUSED", None)
+        assert [r[1] for r in off] == [0, 1, 1] and [r[3] for r in off] == [0, 0, 0], [r[1:] for r in off]
+        assert all(r[2] == chain_k for r in off)
+        for r in off:
+            for x, y, name in zip(r[0], ref[0], ("cost", "S_hat")):
+                assert np.max(np.abs(x - y) / (np.abs(y) + 1e-20)) < 2e-5, name
+    # the plan keeps both signatures' graphs across rebinds: each replay reports its own batch's kernels
+    for counts in (large, small, large, small, large):
+        _, graph, chain_k, w_k = call(eng, counts)
+        assert graph == 1 and (chain_k, w_k) == kernels[len(counts)], (len(counts), graph, chain_k, w_k)
+
+
 def test_label_front_ends_bit_exact():
     """vaenmf.target (csrc/labels.hip) against the reference's own outputs (tests/golden/labels_f257.npz,
     generated by importing python/processing/target.py): every 0/1 label identical, thresholds identical."""
@@ -1134,7 +1191,7 @@ def test_drop_in_object_reuses_its_engine_across_utterances():
 @pytest.mark.parametrize("R,counts", [(30, [21, 64, 130, 9, 65]), (10, [70, 5, 64])])
 def test_fused_w_statistics_equal_the_two_kernel_path(R, counts):
     """wstats_fused_kernel (W statistics and the W update's sums over frames in one pass, one partial per <= 64-frame tile,
-    mcem.py:107-110) against wstats_rot + w_partial + w_update from the same store: the same W, normalisation and --
+    mcem.py:107-110) against wstats_stream2 + w_partial + w_update from the same store: the same W, normalisation and --
     through the H/g kernel that follows -- H, g, cost, up to the order of the float sums over frames (2e-5); ragged
     utterances: tiles of 64, 2, 1 frames, wavefronts without frames.  The fused path is reproducible bit for bit."""
     need_gpu()
