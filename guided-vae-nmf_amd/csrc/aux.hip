@@ -1,6 +1,7 @@
 // Small kernels around the hot loop: W multiplicative update, cost reduction,
 // dense layers (encoder / classifier), |X|^2, STFT / iSTFT, SI-SDR Gram sums.
 #include "common.h"
+#include "fft_lds.h"
 
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4p;
 
@@ -272,24 +273,6 @@ __global__ void nmf_init_kernel(float* __restrict__ W, float* __restrict__ Ht, f
 // ----------------------------------------------------------------------------
 // STFT / iSTFT (python/processing/stft.py -> librosa): radix-2 FFT in LDS, fp64.
 // ----------------------------------------------------------------------------
-__device__ __forceinline__ int bitrev(int x, int bits) { return (int)(__brev((unsigned)x) >> (32 - bits)); }
-
-// in-place complex FFT of length n (power of two) on LDS arrays; sign = -1 forward, +1 inverse
-__device__ void fft_lds(double* re, double* im, const double* twr, const double* twi, int n, int bits, int sign) {
-  for (int len = 2, st = n >> 1, lh = 0; len <= n; len <<= 1, st >>= 1, ++lh) {
-    const int half = len >> 1;                     // = 1 << lh
-    for (int b = threadIdx.x; b < (n >> 1); b += blockDim.x) {
-      const int grp = b >> lh, pos = b & (half - 1);
-      const int i0 = grp * len + pos, i1 = i0 + half;
-      const double wr = twr[pos * st], wi = sign * twi[pos * st];
-      const double xr = re[i1] * wr - im[i1] * wi, xi = re[i1] * wi + im[i1] * wr;
-      re[i1] = re[i0] - xr; im[i1] = im[i0] - xi;
-      re[i0] += xr;         im[i0] += xi;
-    }
-    __syncthreads();
-  }
-}
-
 __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ wav, const int64_t* __restrict__ samp_off,
                                                    const int32_t* __restrict__ frame_off, const int32_t* __restrict__ frame_utt,
                                                    const int32_t* __restrict__ pad_len, int nfft, int bits, int hop, int Fs,
@@ -499,24 +482,18 @@ extern "C" int vaenmf_init_nmf(vaenmf_plan* p, float* W, float* Ht, float* g, ui
 
 extern "C" int vaenmf_stft_num_frames(int64_t n_samples, double fs, double wlen_sec, double hop_percent, int32_t* nfft,
                                       int32_t* hop, int32_t* n_frames, int32_t* n_padded) {
-  VN_REQUIRE(wlen_sec * fs == (double)(int64_t)(wlen_sec * fs), "wlen_sample of STFT is not an integer.");  // stft.py:37-38
-  const int nf = (int)(wlen_sec * fs);
-  const int hp = (int)(hop_percent * nf);
-  VN_REQUIRE(nf >= 16 && nf <= 2048 && (nf & (nf - 1)) == 0, "n_fft=%d: this build needs a power of two in [16,2048]", nf);
-  VN_REQUIRE(hp > 0, "hop must be positive");
-  const double utt_len = (double)n_samples / fs;                                                            // stft.py:49
-  const double ratio = utt_len / wlen_sec / hop_percent;
-  int64_t Tp = n_samples;
-  if (ceil(ratio) != (double)(int64_t)ratio) Tp += hp;                                                      // stft.py:50-51
-  *nfft = nf; *hop = hp; *n_padded = (int32_t)Tp; *n_frames = (int32_t)(1 + Tp / hp);
-  return 0;
+  return vaenmf_stft_geometry(n_samples, fs, wlen_sec, hop_percent, 1, nfft, hop, n_frames, n_padded);
 }
 
 extern "C" int vaenmf_stft_batch(const float* wav, int32_t n_frames_total, const int64_t* sample_offsets,
                                  const int32_t* frame_offsets, const int32_t* frame_utt, const int32_t* padded_len,
                                  int32_t nfft, int32_t hop, int32_t Fs, float* X, void* stream) {
   VN_REQUIRE(wav && X && n_frames_total > 0, "vaenmf_stft_batch: bad arguments");
-  VN_REQUIRE((nfft & (nfft - 1)) == 0 && nfft <= 2048 && Fs >= nfft / 2 + 1, "vaenmf_stft_batch: bad nfft/Fs");
+  if ((nfft & (nfft - 1)) != 0 || nfft > 2048) {          // other lengths: fft.hip
+    const vaenmf_stft_opts o{nfft, hop, 1, VAENMF_PAD_REFLECT, nullptr};
+    return vaenmf_stft_batch_ex(wav, n_frames_total, sample_offsets, frame_offsets, frame_utt, padded_len, &o, Fs, X, stream);
+  }
+  VN_REQUIRE(nfft >= 16 && Fs >= nfft / 2 + 1, "vaenmf_stft_batch: bad nfft/Fs");
   const size_t lds = (size_t)nfft * 3 * sizeof(double);
   hipLaunchKernelGGL(stft_kernel, dim3(n_frames_total), dim3(256), lds, (hipStream_t)stream, wav, sample_offsets,
                      frame_offsets, frame_utt, padded_len, nfft, ilog2(nfft), hop, Fs, reinterpret_cast<float2*>(X));
@@ -528,7 +505,11 @@ extern "C" int vaenmf_istft_batch(const float* S, int32_t n_utt, int32_t n_frame
                                   const int32_t* frame_offsets, int32_t nfft, int32_t hop, int32_t Fs, float* work,
                                   float* wav_out, void* stream) {
   VN_REQUIRE(S && work && wav_out && n_utt > 0, "vaenmf_istft_batch: bad arguments");
-  VN_REQUIRE((nfft & (nfft - 1)) == 0 && nfft <= 2048 && Fs >= nfft / 2 + 1, "vaenmf_istft_batch: bad nfft/Fs");
+  if ((nfft & (nfft - 1)) != 0 || nfft > 2048) {          // other lengths: fft.hip
+    const vaenmf_stft_opts o{nfft, hop, 1, VAENMF_PAD_REFLECT, nullptr};
+    return vaenmf_istft_batch_ex(S, n_utt, n_frames_total, sample_offsets, frame_offsets, &o, Fs, work, wav_out, stream);
+  }
+  VN_REQUIRE(nfft >= 16 && Fs >= nfft / 2 + 1, "vaenmf_istft_batch: bad nfft/Fs");
   const size_t lds = (size_t)nfft * 3 * sizeof(double);
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(istft_frames_kernel, dim3(n_frames_total), dim3(256), lds, st, reinterpret_cast<const float2*>(S), nfft,

@@ -22,6 +22,14 @@ class Rng(C.Structure):
     _fields_ = [("mode", C.c_int32), ("call", C.c_uint32), ("eps", C.c_void_p), ("u", C.c_void_p)]
 
 
+PAD_REFLECT, PAD_CONSTANT = 0, 1
+
+
+class StftOpts(C.Structure):
+    _fields_ = [("nfft", C.c_int32), ("hop", C.c_int32), ("center", C.c_int32), ("pad_mode", C.c_int32),
+                ("window", C.c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol include/vaenmf.h declares
 _P, _I, _I64, _F, _D = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 SIGNATURES = {
@@ -47,9 +55,12 @@ SIGNATURES = {
     "vaenmf_em_run": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
     "vaenmf_dense": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _I, _P]),
     "vaenmf_power_spec": (_I, [_P, _P, _I64, _P]),
+    "vaenmf_stft_geometry": (_I, [_I64, _D, _D, _D, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "vaenmf_stft_num_frames": (_I, [_I64, _D, _D, _D, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "vaenmf_stft_batch": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "vaenmf_stft_batch_ex": (_I, [_P, _I, _P, _P, _P, _P, C.POINTER(StftOpts), _I, _P, _P]),
     "vaenmf_istft_batch": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "vaenmf_istft_batch_ex": (_I, [_P, _I, _I, _P, _P, C.POINTER(StftOpts), _I, _P, _P, _P]),
     "vaenmf_lorenz_work_bytes": (_I64, [_I, _I, _I, _I]),
     "vaenmf_lorenz_labels": (_I, [_P, _I, _P, _I, _I, _I, _F, _F, _F, _P, _I, _P, _P, _I64, _P]),
     "vaenmf_wiener_mask": (_I, [_P, _P, _I64, _F, _P, _P]),
