@@ -1,7 +1,6 @@
 // Small kernels around the hot loop: W multiplicative update, cost reduction,
-// dense layers (encoder / classifier), |X|^2, STFT / iSTFT, SI-SDR Gram sums.
+// dense layers (encoder / classifier), |X|^2, NMF initialisation, SI-SDR Gram sums.
 #include "common.h"
-#include "fft_lds.h"
 
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4p;
 
@@ -270,105 +269,6 @@ __global__ void nmf_init_kernel(float* __restrict__ W, float* __restrict__ Ht, f
   }
 }
 
-// ----------------------------------------------------------------------------
-// STFT / iSTFT (python/processing/stft.py -> librosa): radix-2 FFT in LDS, fp64.
-// ----------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ wav, const int64_t* __restrict__ samp_off,
-                                                   const int32_t* __restrict__ frame_off, const int32_t* __restrict__ frame_utt,
-                                                   const int32_t* __restrict__ pad_len, int nfft, int bits, int hop, int Fs,
-                                                   float2* __restrict__ X) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  double* re = reinterpret_cast<double*>(smem);
-  double* im = re + nfft;
-  double* twr = im + nfft;
-  double* twi = twr + nfft / 2;
-  const int n = blockIdx.x, u = frame_utt[n], i = n - frame_off[u];
-  const int64_t off = samp_off[u];
-  const int64_t T = samp_off[u + 1] - off;
-  const int64_t Tp = pad_len[u];                 // length after the end-pad rule (stft.py:48-53)
-  for (int t = threadIdx.x; t < nfft / 2; t += blockDim.x) {
-    double s, c;
-    sincospi(-2.0 * t / nfft, &s, &c);           // exp(-2 pi i t / nfft)
-    twr[t] = c; twi[t] = s;
-  }
-  __syncthreads();
-  for (int t = threadIdx.x; t < nfft; t += blockDim.x) {
-    int64_t p = (int64_t)i * hop + t - nfft / 2;  // centre=True, reflect padding
-    if (p < 0) p = -p;
-    if (p >= Tp) p = 2 * (Tp - 1) - p;
-    const double v = (p >= 0 && p < T) ? (double)wav[off + p] : 0.0;
-    // cos(2 pi t / nfft) from the twiddle table (two thirds of this kernel's time went into a second fp64 sincospi per sample)
-    const double cw = t < nfft / 2 ? twr[t] : -twr[t - nfft / 2];
-    const int r = bitrev(t, bits);
-    re[r] = v * (0.5 - 0.5 * cw);                 // periodic Hann
-    im[r] = 0.0;
-  }
-  __syncthreads();
-  fft_lds(re, im, twr, twi, nfft, bits, 1);       // table holds exp(-i..): sign +1 keeps it
-  const int F = nfft / 2 + 1;
-  for (int f = threadIdx.x; f < Fs; f += blockDim.x)
-    X[(size_t)n * Fs + f] = f < F ? make_float2((float)re[f], (float)im[f]) : make_float2(0.f, 0.f);
-}
-
-__global__ __launch_bounds__(256) void istft_frames_kernel(const float2* __restrict__ S, int nfft, int bits, int Fs,
-                                                           float* __restrict__ work) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  double* re = reinterpret_cast<double*>(smem);
-  double* im = re + nfft;
-  double* twr = im + nfft;
-  double* twi = twr + nfft / 2;
-  const int n = blockIdx.x;
-  for (int t = threadIdx.x; t < nfft / 2; t += blockDim.x) {
-    double s, c;
-    sincospi(2.0 * t / nfft, &s, &c);             // exp(+2 pi i t / nfft)
-    twr[t] = c; twi[t] = s;
-  }
-  const int half = nfft / 2;
-  for (int k = threadIdx.x; k < nfft; k += blockDim.x) {
-    const int kk = k <= half ? k : nfft - k;
-    const float2 v = S[(size_t)n * Fs + kk];
-    double vr = v.x, vi = (k <= half) ? v.y : -v.y;
-    if (k == 0 || k == half) vi = 0.0;            // c2r ignores the imaginary part of DC / Nyquist
-    const int r = bitrev(k, bits);
-    re[r] = vr; im[r] = vi;
-  }
-  __syncthreads();
-  fft_lds(re, im, twr, twi, nfft, bits, 1);
-  for (int t = threadIdx.x; t < nfft; t += blockDim.x) {
-    const double cw = t < nfft / 2 ? twr[t] : -twr[t - nfft / 2];     // cos(2 pi t / nfft), see stft_kernel
-    work[(size_t)n * nfft + t] = (float)(re[t] / nfft * (0.5 - 0.5 * cw));
-  }
-}
-
-__global__ void istft_ola_kernel(const float* __restrict__ work, const int64_t* __restrict__ samp_off,
-                                 const int32_t* __restrict__ frame_off, int n_utt, int nfft, int hop,
-                                 float* __restrict__ out) {
-  const int u = blockIdx.y;
-  const int64_t off = samp_off[u], T = samp_off[u + 1] - off;
-  const int nb = frame_off[u], nfr = frame_off[u + 1] - nb;
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < T; t += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t p = t + nfft / 2;
-    float y = 0.f;
-    double wss = 0.0;
-    if (p < (int64_t)nfft + (int64_t)hop * (nfr - 1)) {
-      int64_t i_lo = (p - nfft + hop) / hop;        // ceil((p - nfft + 1)/hop)
-      if (p - nfft + 1 <= 0) i_lo = 0;
-      int64_t i_hi = p / hop;
-      if (i_hi > nfr - 1) i_hi = nfr - 1;
-      for (int64_t i = i_lo; i <= i_hi; ++i) {
-        const int tt = (int)(p - i * hop);
-        double sw, cw;
-        sincospi(2.0 * tt / nfft, &sw, &cw);
-        const double wv = 0.5 - 0.5 * cw;
-        y += work[(size_t)(nb + i) * nfft + tt];
-        wss += wv * wv;
-      }
-      if (wss > 1.1754943508222875e-38) y = (float)(y / wss);
-    }
-    out[off + t] = y;
-  }
-}
-
 // Gram matrix of (s_hat, s, n) per utterance in float64 (python/metrics.py:12-60)
 __global__ __launch_bounds__(256) void gram3_kernel(const float* __restrict__ sh, const float* __restrict__ s,
                                                     const float* __restrict__ nz, const int64_t* __restrict__ samp_off,
@@ -411,8 +311,6 @@ __global__ __launch_bounds__(256) void hbm_read_probe_kernel(const u32x4p* __res
   for (; i < n16; i += 256) { const u32x4p v = buf[i]; acc ^= v[0] ^ v[1] ^ v[2] ^ v[3]; }
   if (acc == 0x9E3779B9u) sink[0] = acc;
 }
-
-int ilog2(int n) { int b = 0; while ((1 << b) < n) ++b; return b; }
 
 }  // namespace
 
@@ -476,45 +374,6 @@ extern "C" int vaenmf_init_nmf(vaenmf_plan* p, float* W, float* Ht, float* g, ui
   const size_t n = (size_t)p->n_utt * p->Fs * p->Kp + (size_t)p->NT * p->Kp + (size_t)p->NT;
   hipLaunchKernelGGL(nmf_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, W, Ht, g, p->d_utt_seed,
                      p->d_frame_utt, p->d_frame_loc, p->n_utt, p->NT, p->cfg.F, p->Fs, p->cfg.K, p->Kp, salt, eps);
-  VN_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-extern "C" int vaenmf_stft_num_frames(int64_t n_samples, double fs, double wlen_sec, double hop_percent, int32_t* nfft,
-                                      int32_t* hop, int32_t* n_frames, int32_t* n_padded) {
-  return vaenmf_stft_geometry(n_samples, fs, wlen_sec, hop_percent, 1, nfft, hop, n_frames, n_padded);
-}
-
-extern "C" int vaenmf_stft_batch(const float* wav, int32_t n_frames_total, const int64_t* sample_offsets,
-                                 const int32_t* frame_offsets, const int32_t* frame_utt, const int32_t* padded_len,
-                                 int32_t nfft, int32_t hop, int32_t Fs, float* X, void* stream) {
-  VN_REQUIRE(wav && X && n_frames_total > 0, "vaenmf_stft_batch: bad arguments");
-  if ((nfft & (nfft - 1)) != 0 || nfft > 2048) {          // other lengths: fft.hip
-    const vaenmf_stft_opts o{nfft, hop, 1, VAENMF_PAD_REFLECT, nullptr};
-    return vaenmf_stft_batch_ex(wav, n_frames_total, sample_offsets, frame_offsets, frame_utt, padded_len, &o, Fs, X, stream);
-  }
-  VN_REQUIRE(nfft >= 16 && Fs >= nfft / 2 + 1, "vaenmf_stft_batch: bad nfft/Fs");
-  const size_t lds = (size_t)nfft * 3 * sizeof(double);
-  hipLaunchKernelGGL(stft_kernel, dim3(n_frames_total), dim3(256), lds, (hipStream_t)stream, wav, sample_offsets,
-                     frame_offsets, frame_utt, padded_len, nfft, ilog2(nfft), hop, Fs, reinterpret_cast<float2*>(X));
-  VN_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-
-extern "C" int vaenmf_istft_batch(const float* S, int32_t n_utt, int32_t n_frames_total, const int64_t* sample_offsets,
-                                  const int32_t* frame_offsets, int32_t nfft, int32_t hop, int32_t Fs, float* work,
-                                  float* wav_out, void* stream) {
-  VN_REQUIRE(S && work && wav_out && n_utt > 0, "vaenmf_istft_batch: bad arguments");
-  if ((nfft & (nfft - 1)) != 0 || nfft > 2048) {          // other lengths: fft.hip
-    const vaenmf_stft_opts o{nfft, hop, 1, VAENMF_PAD_REFLECT, nullptr};
-    return vaenmf_istft_batch_ex(S, n_utt, n_frames_total, sample_offsets, frame_offsets, &o, Fs, work, wav_out, stream);
-  }
-  VN_REQUIRE(nfft >= 16 && Fs >= nfft / 2 + 1, "vaenmf_istft_batch: bad nfft/Fs");
-  const size_t lds = (size_t)nfft * 3 * sizeof(double);
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(istft_frames_kernel, dim3(n_frames_total), dim3(256), lds, st, reinterpret_cast<const float2*>(S), nfft,
-                     ilog2(nfft), Fs, work);
-  hipLaunchKernelGGL(istft_ola_kernel, dim3(64, n_utt), dim3(256), 0, st, work, sample_offsets, frame_offsets, n_utt, nfft, hop, wav_out);
   VN_CHECK_HIP(hipGetLastError());
   return 0;
 }

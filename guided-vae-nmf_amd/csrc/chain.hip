@@ -33,8 +33,6 @@ __device__ long long g_wc_stamp[32];
 #endif
 namespace {
 
-constexpr int NK = HID / 32;      // k-steps over a hidden layer
-constexpr int NTH = HID / 16;     // feature tiles of a hidden layer
 constexpr int WT_FRAMES = 16;     // frames per wavefront
 constexpr unsigned WC_OOB = 0xF0000000u;   // byte offset behind every buffer of the chain (the host keeps them below 3.5 GB)
 constexpr int WC_PF = 1;          // tiles of weight fragments (and bias) in flight ahead of the MFMAs that use them
@@ -73,8 +71,8 @@ template <bool SPLIT>
 struct WcLds {
   static constexpr int PARTS = SPLIT ? 2 : 1;
   static constexpr int W1 = 0;                                  // [8][PARTS][1 KB]
-  static constexpr int W2 = W1 + NTH * PARTS * 1024;            // [8][4][PARTS][1 KB]
-  static constexpr int B1 = W2 + NTH * NK * PARTS * 1024;       // float[128]
+  static constexpr int W2 = W1 + NT_H * PARTS * 1024;            // [8][4][PARTS][1 KB]
+  static constexpr int B1 = W2 + NT_H * NK_H * PARTS * 1024;       // float[128]
   static constexpr int B2 = B1 + HID * 4;
   static constexpr int B3 = B2 + HID * 4;                       // float[16 * 40]
   static constexpr int W3 = B3 + 640 * 4;                       // hi blocks [tile][kstep][1 KB] of the first n_hi_lds tiles,
@@ -110,14 +108,6 @@ __device__ __forceinline__ f32x4 tanh4(const f32x4 a) {
   const f32x2 h0 = m2 * r0 + one, h1 = m2 * r1 + one;
   return f32x4{h0[0], h0[1], h1[0], h1[1]};
 }
-template <bool SPLIT>
-__device__ __forceinline__ f32x4 mma(const bf16x8 whi, const bf16x8 wlo, const bf16x8 ahi, const bf16x8 alo, f32x4 acc) {
-  if (SPLIT) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlo, ahi, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(whi, alo, acc, 0, 0, 0);
-  }
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(whi, ahi, acc, 0, 0, 0);
-}
 
 // MAXT : compile-time bound of the bin tiles; EXACT: NT3 == MAXT (no per-tile checks)
 // LOL  : the lo fragments of W3 are in LDS too (bf16x3 mode, small F); otherwise they stream from L2
@@ -147,17 +137,17 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
             *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(srcp) + ((size_t)(b * 2 + part) * 64 + chunk) * 16);
       }
     };
-    stage(smem + L::W1, a.w1f, NTH);
-    stage(smem + L::W2, a.w2f, NTH * NK);
-    for (int e = threadIdx.x; e < n_hi * NK * 64; e += nthr) {      // hi blocks of W3 (tiles GT..)
-      const int chunk = e & 63, b = (e >> 6) + GT * NK;
+    stage(smem + L::W1, a.w1f, NT_H);
+    stage(smem + L::W2, a.w2f, NT_H * NK_H);
+    for (int e = threadIdx.x; e < n_hi * NK_H * 64; e += nthr) {      // hi blocks of W3 (tiles GT..)
+      const int chunk = e & 63, b = (e >> 6) + GT * NK_H;
       *reinterpret_cast<f32x4*>(smem + L::W3 + (size_t)e * 16) =
           *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(a.w3f) + ((size_t)(b * 2) * 64 + chunk) * 16);
     }
     if (SPLIT && LOL)
-      for (int e = threadIdx.x; e < NT3 * NK * 64; e += nthr) {     // lo blocks of W3, behind the hi blocks
+      for (int e = threadIdx.x; e < NT3 * NK_H * 64; e += nthr) {     // lo blocks of W3, behind the hi blocks
         const int chunk = e & 63, b = e >> 6;
-        *reinterpret_cast<f32x4*>(smem + L::W3 + (size_t)n_hi * NK * 1024 + (size_t)e * 16) =
+        *reinterpret_cast<f32x4*>(smem + L::W3 + (size_t)n_hi * NK_H * 1024 + (size_t)e * 16) =
             *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(a.w3f) + ((size_t)(b * 2 + 1) * 64 + chunk) * 16);
       }
     float* b1s = reinterpret_cast<float*>(smem + L::B1);
@@ -173,7 +163,7 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
   const float* b1l = reinterpret_cast<const float*>(smem + L::B1);
   const float* b2l = reinterpret_cast<const float*>(smem + L::B2);
   const float* b3l = reinterpret_cast<const float*>(smem + L::B3);
-  const char* w3lo_lds = smem + L::W3 + (size_t)n_hi * NK * 1024;
+  const char* w3lo_lds = smem + L::W3 + (size_t)n_hi * NK_H * 1024;
   const char* w3g = reinterpret_cast<const char*>(a.w3f);
   const int S = a.nsamples + a.burnin;
   // first of this lane's 4 consecutive bins in tile t
@@ -246,11 +236,11 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
       }
     }
     constexpr bool B1L = M2 && NWAVES == 8;                // layer-1 bias rows parked in LDS (see above)
-    f32x4 b1r[(M2 && !B1L) ? NTH : 1];                     // M2: layer-1 accumulator init of this lane's frame
-    char* b1stash = smem + a.b1_lds + wave * (NTH * 512) + lane * 8;     // [tile][lane][4 bf16], this lane's words only
+    f32x4 b1r[(M2 && !B1L) ? NT_H : 1];                     // M2: layer-1 accumulator init of this lane's frame
+    char* b1stash = smem + a.b1_lds + wave * (NT_H * 512) + lane * 8;     // [tile][lane][4 bf16], this lane's words only
     if (M2) {
 #pragma unroll
-      for (int t = 0; t < NTH; ++t) {
+      for (int t = 0; t < NT_H; ++t) {
         const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(b1in_rs, ((unsigned)nrow * HID + 4u * (unsigned)q) * 4u + 64u * (unsigned)t, 0, 0));
         if (B1L) *reinterpret_cast<u32x2*>(b1stash + t * 512) = u32x2{pk2(v[0], v[1]), pk2(v[2], v[3])};
         else b1r[(M2 && !B1L) ? t : 0] = v;
@@ -303,8 +293,8 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
       // in the first dword of the 16-byte stores).
       const unsigned voff = DOST ? fbase + (unsigned)slot * (unsigned)a.Fs * (unsigned)sizeof(store_t) : 0u;
       // B fragments of a layer's input: k-step s <-> feature tiles 2s (elements 0..3) and 2s+1 (elements 4..7)
-      u32x4 bh[NK], bl[NK], ch[NK], cl[NK];
-      auto put = [&](u32x4 (&dh)[NK], u32x4 (&dl)[NK], int t, const f32x4 h) {      // tile t of the next layer's input
+      u32x4 bh[NK_H], bl[NK_H], ch[NK_H], cl[NK_H];
+      auto put = [&](u32x4 (&dh)[NK_H], u32x4 (&dl)[NK_H], int t, const f32x4 h) {      // tile t of the next layer's input
         dh[t >> 1][2 * (t & 1)] = pk2(h[0], h[1]);
         dh[t >> 1][2 * (t & 1) + 1] = pk2(h[2], h[3]);
         if (SPLIT) {
@@ -353,7 +343,7 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
             for (int s = 0; s < NKS; ++s) {
               bf16x8 ah, al;
               bop(s, ah, al);
-              ac = mma<SPLIT>(wh[t % NB][s], SPLIT ? wl[t % NBL][s] : wh[t % NB][s], ah, al, ac);
+              ac = mma3<SPLIT>(wh[t % NB][s], SPLIT ? wl[t % NBL][s] : wh[t % NB][s], ah, al, ac);
             }
             acc[t & 1] = ac;
           }
@@ -379,19 +369,19 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
       // use (the single wavefront of a SIMD otherwise sits out one L2 round trip per evaluation at the head of the output layer)
       // (registers live through the hidden layers: 2 + 2 fits the 512 registers, 3 + 1 spills; 132.5 -> 131.8 ms per bf16x3 step)
       constexpr int NHOIST = (SPLIT && !LOL && !M2) ? 2 : 0;      // (M2 keeps its 32 bias registers instead)
-      bf16x8 lo_pre[NHOIST > 0 ? NHOIST : 1][NK];
+      bf16x8 lo_pre[NHOIST > 0 ? NHOIST : 1][NK_H];
       if (NHOIST > 0) {
 #pragma unroll
         for (int t = 0; t < NHOIST; ++t)
 #pragma unroll
-          for (int s = 0; s < NK; ++s) lo_pre[t][s] = *reinterpret_cast<const bf16x8*>(w3g + (size_t)((t * NK + s) * 2 + 1) * 1024 + l16);
+          for (int s = 0; s < NK_H; ++s) lo_pre[t][s] = *reinterpret_cast<const bf16x8*>(w3g + (size_t)((t * NK_H + s) * 2 + 1) * 1024 + l16);
       }
-      bf16x8 gfr[GT > 0 ? GT : 1][NK];                 // hi fragments of the bin tiles that live in global memory (L2)
+      bf16x8 gfr[GT > 0 ? GT : 1][NK_H];                 // hi fragments of the bin tiles that live in global memory (L2)
       if (GT > 0) {
 #pragma unroll
         for (int t = 0; t < GT; ++t)
 #pragma unroll
-          for (int s = 0; s < NK; ++s) gfr[t][s] = *reinterpret_cast<const bf16x8*>(w3g + (size_t)((t * NK + s) * 2) * 1024 + l16);
+          for (int s = 0; s < NK_H; ++s) gfr[t][s] = *reinterpret_cast<const bf16x8*>(w3g + (size_t)((t * NK_H + s) * 2) * 1024 + l16);
       }
       // ---- layer 1: input = the latents of this lane's frame (one k-step)
       {
@@ -402,7 +392,7 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
           bl[0][2] = pk2(zz[4] - bf_lo(bh[0][2]), zz[5] - bf_hi(bh[0][2]));
           bl[0][3] = pk2(zz[6] - bf_lo(bh[0][3]), zz[7] - bf_hi(bh[0][3]));
         }
-        run_layer(std::integral_constant<int, 1>{}, std::integral_constant<int, NTH>{}, std::integral_constant<int, WC_PF>{},
+        run_layer(std::integral_constant<int, 1>{}, std::integral_constant<int, NT_H>{}, std::integral_constant<int, WC_PF>{},
                   [&](int t, int, bf16x8& hi) { hi = *reinterpret_cast<const bf16x8*>(smem + L::W1 + t * PARTS * 1024 + l16); },
                   [&](int t, int, bf16x8& lo) { lo = *reinterpret_cast<const bf16x8*>(smem + L::W1 + t * PARTS * 1024 + (SPLIT ? 1024 : 0) + l16); },
                   [&](int t, int, bf16x8& lo) { lo = *reinterpret_cast<const bf16x8*>(smem + L::W1 + t * PARTS * 1024 + (SPLIT ? 1024 : 0) + l16); },
@@ -420,12 +410,12 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
       // ---- layer 2 (a decoder with ONE hidden layer, models.py:107-121 with h_dim = [128], hands layer 1's output on)
       if (a.one_hidden) {
 #pragma unroll
-        for (int s = 0; s < NK; ++s) { bh[s] = ch[s]; if (SPLIT) bl[s] = cl[s]; }
+        for (int s = 0; s < NK_H; ++s) { bh[s] = ch[s]; if (SPLIT) bl[s] = cl[s]; }
       } else
-      run_layer(std::integral_constant<int, NK>{}, std::integral_constant<int, NTH>{}, std::integral_constant<int, WC_PF>{},
-                [&](int t, int s, bf16x8& hi) { hi = *reinterpret_cast<const bf16x8*>(smem + L::W2 + (t * NK + s) * PARTS * 1024 + l16); },
-                [&](int t, int s, bf16x8& lo) { lo = *reinterpret_cast<const bf16x8*>(smem + L::W2 + (t * NK + s) * PARTS * 1024 + (SPLIT ? 1024 : 0) + l16); },
-                [&](int t, int s, bf16x8& lo) { lo = *reinterpret_cast<const bf16x8*>(smem + L::W2 + (t * NK + s) * PARTS * 1024 + (SPLIT ? 1024 : 0) + l16); },
+      run_layer(std::integral_constant<int, NK_H>{}, std::integral_constant<int, NT_H>{}, std::integral_constant<int, WC_PF>{},
+                [&](int t, int s, bf16x8& hi) { hi = *reinterpret_cast<const bf16x8*>(smem + L::W2 + (t * NK_H + s) * PARTS * 1024 + l16); },
+                [&](int t, int s, bf16x8& lo) { lo = *reinterpret_cast<const bf16x8*>(smem + L::W2 + (t * NK_H + s) * PARTS * 1024 + (SPLIT ? 1024 : 0) + l16); },
+                [&](int t, int s, bf16x8& lo) { lo = *reinterpret_cast<const bf16x8*>(smem + L::W2 + (t * NK_H + s) * PARTS * 1024 + (SPLIT ? 1024 : 0) + l16); },
                 [&](int t) { return *reinterpret_cast<const f32x4*>(b2l + 16 * t + 4 * q); },
                 [&](int s, bf16x8& hi, bf16x8& lo) { hi = __builtin_bit_cast(bf16x8, ch[s]); lo = SPLIT ? __builtin_bit_cast(bf16x8, cl[s]) : hi; },
                 [&](int t, const f32x4 acc) { put(bh, bl, t, tanh4(acc)); });
@@ -434,20 +424,20 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
       double e = 0.0;
       f32x2 pl2 = {0.f, 0.f}, px2 = {0.f, 0.f};
       unsigned pk_even0 = 0, pk_even1 = 0;
-      run_layer(std::integral_constant<int, NK>{}, std::integral_constant<int, MAXT>{}, std::integral_constant<int, (SPLIT && !LOL) ? WC_PFL : WC_PF>{},
+      run_layer(std::integral_constant<int, NK_H>{}, std::integral_constant<int, MAXT>{}, std::integral_constant<int, (SPLIT && !LOL) ? WC_PFL : WC_PF>{},
                 [&](int t, int s, bf16x8& hi) {
                   if (GT > 0 && t < GT) hi = gfr[t < GT ? t : 0][s];
-                  else if (HIALL || t - GT < n_hi) hi = *reinterpret_cast<const bf16x8*>(smem + L::W3 + ((t - GT) * NK + s) * 1024 + l16);
-                  else hi = *reinterpret_cast<const bf16x8*>(w3g + (size_t)((t * NK + s) * 2) * 1024 + l16);
+                  else if (HIALL || t - GT < n_hi) hi = *reinterpret_cast<const bf16x8*>(smem + L::W3 + ((t - GT) * NK_H + s) * 1024 + l16);
+                  else hi = *reinterpret_cast<const bf16x8*>(w3g + (size_t)((t * NK_H + s) * 2) * 1024 + l16);
                 },
                 [&](int t, int s, bf16x8& lo) {
-                  if (LOL) lo = *reinterpret_cast<const bf16x8*>(w3lo_lds + (t * NK + s) * 1024 + l16);
-                  else lo = *reinterpret_cast<const bf16x8*>(w3g + (size_t)((t * NK + s) * 2 + 1) * 1024 + l16);
+                  if (LOL) lo = *reinterpret_cast<const bf16x8*>(w3lo_lds + (t * NK_H + s) * 1024 + l16);
+                  else lo = *reinterpret_cast<const bf16x8*>(w3g + (size_t)((t * NK_H + s) * 2 + 1) * 1024 + l16);
                 },
                 [&](int t, int s, bf16x8& lo) {           // the first tiles' lo fragments: requested at the top of the evaluation (NHOIST)
-                  if (LOL) lo = *reinterpret_cast<const bf16x8*>(w3lo_lds + (t * NK + s) * 1024 + l16);
+                  if (LOL) lo = *reinterpret_cast<const bf16x8*>(w3lo_lds + (t * NK_H + s) * 1024 + l16);
                   else if (t < NHOIST) lo = lo_pre[t < NHOIST ? t : 0][s];
-                  else lo = *reinterpret_cast<const bf16x8*>(w3g + (size_t)((t * NK + s) * 2 + 1) * 1024 + l16);
+                  else lo = *reinterpret_cast<const bf16x8*>(w3g + (size_t)((t * NK_H + s) * 2 + 1) * 1024 + l16);
                 },
                 [&](int t) { return *reinterpret_cast<const f32x4*>(b3l + 16 * t + 4 * q); },
                 [&](int s, bf16x8& hi, bf16x8& lo) { hi = __builtin_bit_cast(bf16x8, bh[s]); lo = SPLIT ? __builtin_bit_cast(bf16x8, bl[s]) : hi; },
@@ -609,7 +599,7 @@ __global__ __launch_bounds__(256, 1) void wchain4_kernel(const WcArgs a) {
   // ---- this wavefront's weight fragments and biases, in registers for the whole launch (fragment order
   // [tile][kstep][hi/lo][lane][8], plan.hip): 2 hidden tiles per hidden layer, NOWN bin tiles -- no LDS-resident weights,
   // no weight loads inside the chain
-  bf16x8 w1r[2], w2r[2][NK], w3r[NOWN][NK];
+  bf16x8 w1r[2], w2r[2][NK_H], w3r[NOWN][NK_H];
   f32x4 bias1[2], bias2[2], bias3[NOWN];
   {
     const char* w1g = reinterpret_cast<const char*>(a.w1f);
@@ -620,7 +610,7 @@ __global__ __launch_bounds__(256, 1) void wchain4_kernel(const WcArgs a) {
       const int t = 2 * wave + i;
       w1r[i] = *reinterpret_cast<const bf16x8*>(w1g + (size_t)(t * 2) * 1024 + l16);
 #pragma unroll
-      for (int s = 0; s < NK; ++s) w2r[i][s] = *reinterpret_cast<const bf16x8*>(w2g + (size_t)((t * NK + s) * 2) * 1024 + l16);
+      for (int s = 0; s < NK_H; ++s) w2r[i][s] = *reinterpret_cast<const bf16x8*>(w2g + (size_t)((t * NK_H + s) * 2) * 1024 + l16);
       bias1[i] = *reinterpret_cast<const f32x4*>(a.b1 + 16 * t + 4 * q);
       bias2[i] = *reinterpret_cast<const f32x4*>(a.b2 + 16 * t + 4 * q);
     }
@@ -628,7 +618,7 @@ __global__ __launch_bounds__(256, 1) void wchain4_kernel(const WcArgs a) {
     for (int i = 0; i < NOWN; ++i) {
       const int t = tile_of(i);
 #pragma unroll
-      for (int s = 0; s < NK; ++s) w3r[i][s] = *reinterpret_cast<const bf16x8*>(w3g + (size_t)((t * NK + s) * 2) * 1024 + l16);
+      for (int s = 0; s < NK_H; ++s) w3r[i][s] = *reinterpret_cast<const bf16x8*>(w3g + (size_t)((t * NK_H + s) * 2) * 1024 + l16);
       bias3[i] = *reinterpret_cast<const f32x4*>(a.b3 + 16 * t + 4 * q);
     }
   }
@@ -720,16 +710,16 @@ __global__ __launch_bounds__(256, 1) void wchain4_kernel(const WcArgs a) {
     auto energy = [&](const float (&zz)[8], int slot, auto dost) -> double {
       constexpr bool DOST = STORE && decltype(dost)::value;
       const unsigned voff = DOST ? fbase + (unsigned)slot * (unsigned)a.Fs * 2u : 0u;
-      u32x4 bh[NK], ch[NK];
+      u32x4 bh[NK_H], ch[NK_H];
       // hidden layers: this wavefront computes feature tiles 2w, 2w+1 -- after tanh and the bf16 rounding exactly k-step w of
       // the next layer's input fragments (file header) -- and the four k-steps are exchanged through LDS
       u32x4 mine;
       auto put2 = [&](int i, const f32x4 h) { mine[2 * i] = pk2(h[0], h[1]); mine[2 * i + 1] = pk2(h[2], h[3]); };
-      auto exchange = [&](u32x4* xh, u32x4 (&dst)[NK]) {
+      auto exchange = [&](u32x4* xh, u32x4 (&dst)[NK_H]) {
         xh[wave * 64 + lane] = mine;
         __syncthreads();
 #pragma unroll
-        for (int s2 = 0; s2 < NK; ++s2) dst[s2] = xh[s2 * 64 + lane];
+        for (int s2 = 0; s2 < NK_H; ++s2) dst[s2] = xh[s2 * 64 + lane];
       };
       {
         const bf16x8 zin = __builtin_bit_cast(bf16x8, u32x4{pk2(zz[0], zz[1]), pk2(zz[2], zz[3]), pk2(zz[4], zz[5]), pk2(zz[6], zz[7])});
@@ -742,14 +732,14 @@ __global__ __launch_bounds__(256, 1) void wchain4_kernel(const WcArgs a) {
       exchange(xh1, ch);
       if (a.one_hidden) {
 #pragma unroll
-        for (int s = 0; s < NK; ++s) bh[s] = ch[s];
+        for (int s = 0; s < NK_H; ++s) bh[s] = ch[s];
       } else {
         f32x4 ac[2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
           ac[i] = bias2[i];
 #pragma unroll
-          for (int s = 0; s < NK; ++s) ac[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2r[i][s], __builtin_bit_cast(bf16x8, ch[s]), ac[i], 0, 0, 0);
+          for (int s = 0; s < NK_H; ++s) ac[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2r[i][s], __builtin_bit_cast(bf16x8, ch[s]), ac[i], 0, 0, 0);
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i) put2(i, tanh4(ac[i]));
@@ -764,7 +754,7 @@ __global__ __launch_bounds__(256, 1) void wchain4_kernel(const WcArgs a) {
       auto mm3 = [&](int i) {
         f32x4 ac = bias3[i];
 #pragma unroll
-        for (int s = 0; s < NK; ++s) ac = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w3r[i][s], __builtin_bit_cast(bf16x8, bh[s]), ac, 0, 0, 0);
+        for (int s = 0; s < NK_H; ++s) ac = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w3r[i][s], __builtin_bit_cast(bf16x8, bh[s]), ac, 0, 0, 0);
         return ac;
       };
       auto epi = [&](int i, const f32x4 acc) {
@@ -890,16 +880,12 @@ __global__ __launch_bounds__(256, 1) void wchain4_kernel(const WcArgs a) {
 // ============================================================================
 // Host side
 // ============================================================================
-int vn_ensure_dyn_lds(const void* fn, int bytes);     // plan.hip: per-device hipFuncSetAttribute, checked
-
 namespace {
-
-constexpr int WC_LDS_LIMIT = 160 * 1024;
 
 template <int MAXT, bool EXACT, bool SPLIT, bool STORE, int NWAVES, bool LOL, bool HIALL, bool M2, int GT = 0>
 int wc_launch(const WcArgs& a, int grid, size_t lds, hipStream_t st) {
   auto* fn = wchain_kernel<MAXT, EXACT, SPLIT, STORE, NWAVES, LOL, HIALL, M2, GT>;
-  if (int e = vn_ensure_dyn_lds((const void*)fn, WC_LDS_LIMIT)) return e;
+  if (int e = vn_ensure_dyn_lds((const void*)fn, VN_LDS_LIMIT)) return e;
   hipLaunchKernelGGL(fn, dim3(grid), dim3(NWAVES * 64), lds, st, a);
   return 0;
 }
@@ -960,13 +946,13 @@ int vn_launch_wchain(vaenmf_plan* p, const VnChainCall& cc, hipStream_t st) {
   a.n_hi_lds = p->NT3c;
   const size_t fixed = split ? WcLds<true>::fixed_bytes : WcLds<false>::fixed_bytes;
   constexpr int GT33 = 4;                                // F = 513: bin tiles whose fragments stay in global memory
-  const size_t w3hi = (size_t)(p->NT3c == 33 ? p->NT3c - GT33 : p->NT3c) * NK * 1024;
+  const size_t w3hi = (size_t)(p->NT3c == 33 ? p->NT3c - GT33 : p->NT3c) * NK_H * 1024;
   const bool lol = split && p->NT3c <= 5;              // bf16x3: the lo fragments of W3 fit in LDS up to 5 tiles (F <= 80), else they stream from L2
   constexpr int NW_BF16 = 8, NW_X3 = 4;
   const int nwaves = (split || p->NT3c == 33) ? 4 : NW_BF16;
   a.b1_lds = (int)(fixed + w3hi * (lol ? 2 : 1));
-  const size_t lds = (size_t)a.b1_lds + ((cc.B1 && nwaves == 8) ? (size_t)nwaves * NTH * 512 : 0);
-  VN_REQUIRE(lds <= (size_t)WC_LDS_LIMIT, "wave chain: %zu bytes of LDS needed", lds);
+  const size_t lds = (size_t)a.b1_lds + ((cc.B1 && nwaves == 8) ? (size_t)nwaves * NT_H * 512 : 0);
+  VN_REQUIRE(lds <= (size_t)VN_LDS_LIMIT, "wave chain: %zu bytes of LDS needed", lds);
   // small batches (at most one wave tile per CU) in bf16 mode at 17 / 33 bin tiles: four wavefronts per wave tile (wchain4_kernel)
   if (!split && (p->NT3c == 17 || p->NT3c == 33) && p->n_wtiles <= p->n_sms && vn_switches().wchain4) {
     const size_t lds4 = 2 * 4 * 64 * 16 + 20 * 64 * 4;          // exchange areas only

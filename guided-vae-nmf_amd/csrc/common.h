@@ -33,6 +33,30 @@ constexpr int VN_COST_CHUNK = 25;     // EM iterations whose per-frame cost sums
 constexpr int MAX_TILE_FRAMES = 64;   // MH chain: frames per workgroup = 32 per team (2 MFMA column groups of 16)
 constexpr int LAT = 32;               // latent dimension handled by the MFMA path
 constexpr int HID = 128;              // hidden width of both decoder layers
+constexpr int NK_H = HID / 32;        // k-steps over a hidden layer (4)
+constexpr int NT_H = HID / 16;        // feature tiles of a hidden layer (8)
+constexpr int VN_LDS_LIMIT = 160 * 1024;   // LDS of a CU: the most dynamic LDS a kernel is allowed (vn_ensure_dyn_lds)
+
+// vaenmf_em_run as a HIP graph (driver.hip): the ~600 launches of a call captured once per call signature and replayed, so
+// that the launch path needs the host once per call instead of once per kernel (a loaded host showed as up to 20 % of
+// idle GPU time between the kernels)
+struct VnEmGraphs {
+  using Key = std::vector<uint64_t>;
+  struct Graph {
+    Key key; hipGraphExec_t exec; uint64_t used;
+    int chain_kernel, w_fused;          // last_chain_kernel / last_w_fused as the captured body left them
+  };
+  hipStream_t cap_stream = nullptr;     // capture needs a stream of its own (the caller's may be the null stream)
+  std::vector<Graph> cache;             // captured calls, a few signatures (a job alternates batch shapes: 63 / 62 utterances)
+  std::vector<Key> seen;                // signatures run eagerly once (a signature is captured at its second appearance)
+  uint64_t tick = 0;
+  bool off = false;                     // capture failed once on this plan: stay eager
+  int last = 0;                         // VAENMF_Q_EM_GRAPH: 1 when the last vaenmf_em_run was a graph launch
+  Graph* find(const Key& key);                                          // a captured call of this signature, or null
+  bool first_seen(const Key& key);                                      // true (and remembered) at a signature's first appearance
+  Graph* insert(const Key& key, hipGraphExec_t exec, int chain_kernel, int w_fused);   // evicts the least recently used
+  void release();                                                       // vaenmf_plan_destroy
+};
 
 struct vaenmf_plan {
   vaenmf_config cfg;
@@ -93,25 +117,13 @@ struct vaenmf_plan {
   std::vector<hipEvent_t> prof_ev;      // pairs (start, stop)
   std::vector<int> prof_kind;
   size_t prof_used;
-  // vaenmf_em_run as a HIP graph: the ~600 launches of a call captured once per call signature and replayed, so that
-  // the launch path needs the host once per call instead of once per kernel (a loaded host showed as up to 20 % of
-  // idle GPU time between the kernels)
-  hipStream_t cap_stream = nullptr;     // capture needs a stream of its own (the caller's may be the null stream)
-  struct EmGraph {
-    std::vector<uint64_t> key; hipGraphExec_t exec; uint64_t used;
-    int chain_kernel, w_fused;          // last_chain_kernel / last_w_fused as the captured body left them
-  };
-  std::vector<EmGraph> g_cache;         // captured calls, a few signatures (a job alternates batch shapes: 63 / 62 utterances)
-  std::vector<std::vector<uint64_t>> g_seen;   // signatures run eagerly once (a signature is captured at its second appearance)
-  uint64_t g_tick = 0;
-  bool g_off = false;                   // capture failed once on this plan: stay eager
+  VnEmGraphs graphs;
   // vaenmf_bind_batch_async: the per-batch seeds go up from a ring of pinned slots (a slot is reused when its copy is done)
   static constexpr int SEED_RING = 8;
   uint64_t* h_seed_ring = nullptr;      // pinned [SEED_RING][max_utts]
   hipEvent_t seed_ev[SEED_RING] = {};
   bool seed_ev_used[SEED_RING] = {};
   int seed_pos = 0;
-  int last_em_graph = 0;                // VAENMF_Q_EM_GRAPH: 1 when the last vaenmf_em_run was a graph launch
 };
 
 // one MH-chain call, as vaenmf_mh_chain hands it to the kernel launchers (engine.hip team kernel, chain.hip wave kernel)
@@ -137,7 +149,26 @@ struct VnSwitches {
   int wfused_grid;     // VAENMF_WFUSED_GRID=n: at most n workgroups for wstats_fused_kernel (0: no cap)
   bool keep_zs;        // VAENMF_KEEP_ZS=1: the E-step chains of the sample-store path record their samples anyway
 };
-VnSwitches vn_switches();
+
+// ---- functions one source file defines and another calls (the file that defines each) ----
+VnSwitches vn_switches();                                  // plan.hip
+int vn_ensure_dyn_lds(const void* fn, int bytes);          // plan.hip: per-device hipFuncSetAttribute, checked
+extern long long g_vn_dev_allocs;                          // plan.hip: device allocations made by the library (VAENMF_Q_DEV_ALLOCS)
+bool vn_wchain_supported(const vaenmf_plan* p);            // chain.hip
+bool vn_wchain_fits(const vaenmf_plan* p, const VnChainCall& cc);                 // chain.hip
+int vn_launch_wchain(vaenmf_plan* p, const VnChainCall& cc, hipStream_t st);      // chain.hip: builds WcArgs, picks the kernel
+int vn_launch_tchain(vaenmf_plan* p, const VnChainCall& cc, hipStream_t st);      // engine.hip: builds ChainArgs, picks the geometry
+int vn_launch_w_update(const vaenmf_plan* p, float* W, const float* Ht, hipStream_t st);                // aux.hip
+int vn_launch_w_update_tiles(const vaenmf_plan* p, float* W, hipStream_t st, bool groups);             // aux.hip
+int vn_launch_cost_reduce(const vaenmf_plan* p, const double* cost_frames, size_t stride, int n_it, int R, double* cost, int niter,
+                          int it0, hipStream_t st);                                                     // aux.hip
+
+inline int check_bound(const vaenmf_plan* p) {
+  VN_REQUIRE(p != nullptr, "null plan");
+  VN_REQUIRE(p->have_weights, "decoder weights not set (vaenmf_set_decoder_weights)");
+  VN_REQUIRE(p->NT > 0, "no batch bound (vaenmf_bind_batch)");
+  return 0;
+}
 
 enum { VN_K_CHAIN = 0, VN_K_WSTATS = 1, VN_K_WUPDATE = 2, VN_K_HG = 3, VN_K_WF = 4, VN_K_NKINDS = 5 };
 struct ProfScope {   // records a (start, stop) event pair around a launch when profiling is on
@@ -175,6 +206,17 @@ __device__ __forceinline__ void split4(const f32x4 v, bf16x4& hi, bf16x4& lo) {
     hi[t] = h;
     lo[t] = (__bf16)(v[t] - (float)h);
   }
+}
+
+// one MFMA step of a decoder layer: bf16x3 (SPLIT) adds the two cross terms of the (hi, lo) parts
+template <bool SPLIT>
+__device__ __forceinline__ f32x4 mma3(const bf16x8 whi, const bf16x8 wlo, const bf16x8 ahi, const bf16x8 alo, f32x4 acc) {
+  // weights are the A operand (rows = output features), activations the B operand
+  if (SPLIT) {
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlo, ahi, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(whi, alo, acc, 0, 0, 0);
+  }
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(whi, ahi, acc, 0, 0, 0);
 }
 
 // ---- cross-lane sums without LDS traffic (DPP / permlane-swap VALU ops) ----------------

@@ -16,12 +16,9 @@
 // PREC: bf16x3 computes w_hi*a_hi + w_lo*a_hi + w_hi*a_lo (error ~2^-17 per product);
 //       bf16 computes w_hi*a_hi only.
 #include "common.h"
-#include <cstring>
 
 namespace {
 
-constexpr int NK_H = HID / 32;     // k-steps over a hidden layer (4)
-constexpr int NT_H = HID / 16;     // feature tiles of a hidden layer (8)
 constexpr int TEAM_COLS = 32;      // MLP input rows ("columns") per team and pass: 2 MFMA column groups
 
 struct DecW {                      // decoder weights (device), fragment order [tile][kstep][part][lane][8]
@@ -76,15 +73,6 @@ __device__ __forceinline__ void stage_weights(char* dst, const __bf16* src, int 
   }
 }
 
-template <bool SPLIT>
-__device__ __forceinline__ f32x4 mma3(const bf16x8 whi, const bf16x8 wlo, const bf16x8 ahi, const bf16x8 alo, f32x4 acc) {
-  // weights are the A operand (rows = output features), activations the B operand
-  if (SPLIT) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wlo, ahi, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(whi, alo, acc, 0, 0, 0);
-  }
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(whi, ahi, acc, 0, 0, 0);
-}
 template <bool SPLIT>
 __device__ __forceinline__ f32x4 mma3_flip(const bf16x8 ahi, const bf16x8 alo, const bf16x8 whi, const bf16x8 wlo, f32x4 acc) {
   // activations are the A operand (rows = samples), weights the B operand (cols = features)
@@ -1312,8 +1300,6 @@ __global__ __launch_bounds__(NW * NTEAM * 64) void decode_kernel(const DecodeArg
 // ============================================================================
 // Host launchers (C ABI)
 // ============================================================================
-int vn_ensure_dyn_lds(const void* fn, int bytes);     // plan.hip
-
 namespace {
 
 DecW make_decw(const vaenmf_plan* p) {
@@ -1325,15 +1311,13 @@ DecW make_decw(const vaenmf_plan* p) {
   return d;
 }
 
-constexpr int LDS_LIMIT = 160 * 1024;
-
 // LDS bytes and W3 placement: W3 fragments go to LDS when they fit, else stream from L2
 template <int NTEAM, bool SPLIT>
 void lds_plan(int NT3, size_t extra_per_team, int* w3_off, size_t* total) {
   using M = LdsMap<NTEAM, SPLIT>;
   const size_t base = (M::common_end + NTEAM * extra_per_team + 15) / 16 * 16;
   const size_t w3 = M::w3_bytes(NT3);
-  if (base + w3 <= (size_t)LDS_LIMIT) { *w3_off = (int)base; *total = base + w3; }
+  if (base + w3 <= (size_t)VN_LDS_LIMIT) { *w3_off = (int)base; *total = base + w3; }
   else { *w3_off = -1; *total = base; }
 }
 
@@ -1343,10 +1327,10 @@ int launch_chain_s(ChainArgs a, int n_tiles, hipStream_t st) {
   lds_plan<NTEAM, SPLIT>(a.dw.NT3, sizeof(ChainX), &a.w3_lds_off, &lds);
   const dim3 blk(NW * NTEAM * 64);
   if (a.w3_lds_off >= 0) {
-    if (int e = vn_ensure_dyn_lds((const void*)mh_chain_kernel<NW, NTEAM, MT, SPLIT, true, STORE>, LDS_LIMIT)) return e;
+    if (int e = vn_ensure_dyn_lds((const void*)mh_chain_kernel<NW, NTEAM, MT, SPLIT, true, STORE>, VN_LDS_LIMIT)) return e;
     hipLaunchKernelGGL((mh_chain_kernel<NW, NTEAM, MT, SPLIT, true, STORE>), dim3(n_tiles), blk, lds, st, a);
   } else {
-    if (int e = vn_ensure_dyn_lds((const void*)mh_chain_kernel<NW, NTEAM, MT, SPLIT, false, STORE>, LDS_LIMIT)) return e;
+    if (int e = vn_ensure_dyn_lds((const void*)mh_chain_kernel<NW, NTEAM, MT, SPLIT, false, STORE>, VN_LDS_LIMIT)) return e;
     hipLaunchKernelGGL((mh_chain_kernel<NW, NTEAM, MT, SPLIT, false, STORE>), dim3(n_tiles), blk, lds, st, a);
   }
   return 0;
@@ -1360,10 +1344,10 @@ template <int NW, int NTEAM, int MT, bool SPLIT, int MODE, int KP>
 int launch_decode_one(const DecodeArgs& a, int grid, size_t lds, hipStream_t st) {
   const dim3 blk(NW * NTEAM * 64);
   if (a.w3_lds_off >= 0) {
-    if (int e = vn_ensure_dyn_lds((const void*)decode_kernel<NW, NTEAM, MT, SPLIT, true, MODE, KP>, LDS_LIMIT)) return e;
+    if (int e = vn_ensure_dyn_lds((const void*)decode_kernel<NW, NTEAM, MT, SPLIT, true, MODE, KP>, VN_LDS_LIMIT)) return e;
     hipLaunchKernelGGL((decode_kernel<NW, NTEAM, MT, SPLIT, true, MODE, KP>), dim3(grid), blk, lds, st, a);
   } else {
-    if (int e = vn_ensure_dyn_lds((const void*)decode_kernel<NW, NTEAM, MT, SPLIT, false, MODE, KP>, LDS_LIMIT)) return e;
+    if (int e = vn_ensure_dyn_lds((const void*)decode_kernel<NW, NTEAM, MT, SPLIT, false, MODE, KP>, VN_LDS_LIMIT)) return e;
     hipLaunchKernelGGL((decode_kernel<NW, NTEAM, MT, SPLIT, false, MODE, KP>), dim3(grid), blk, lds, st, a);
   }
   return 0;
@@ -1407,68 +1391,20 @@ DecodeArgs base_decode_args(const vaenmf_plan* p, const float* Zs, int Rcap, int
   return a;
 }
 
-int check_bound(const vaenmf_plan* p) {
-  VN_REQUIRE(p != nullptr, "null plan");
-  VN_REQUIRE(p->have_weights, "decoder weights not set (vaenmf_set_decoder_weights)");
-  VN_REQUIRE(p->NT > 0, "no batch bound (vaenmf_bind_batch)");
-  return 0;
-}
-
 }  // namespace
 
-extern long long g_vn_dev_allocs;      // plan.hip
-// chain.hip
-bool vn_wchain_supported(const vaenmf_plan* p);
-bool vn_wchain_fits(const vaenmf_plan* p, const VnChainCall& cc);
-int vn_launch_wchain(vaenmf_plan* p, const VnChainCall& cc, hipStream_t st);
-// aux.hip
-int vn_launch_w_update(const vaenmf_plan* p, float* W, const float* Ht, hipStream_t st);
-int vn_launch_cost_reduce(const vaenmf_plan* p, const double* cost_frames, size_t stride, int n_it, int R, double* cost, int niter, int it0, hipStream_t st);
-
-extern "C" int vaenmf_mh_chain(vaenmf_plan* p, const float* X2, const float* W, const float* Ht, const float* g,
-                               float* Z, int32_t update_Z, const float* B1, float* Zs, int32_t Rcap, int32_t nsamples,
-                               int32_t burnin, float var_rw, const vaenmf_rng* rng, float* acc_out, void* stream) {
-  if (int e = check_bound(p)) return e;
-  VN_REQUIRE(rng != nullptr, "rng is null");
-  VN_REQUIRE(nsamples >= 1 && burnin >= 0 && nsamples <= Rcap, "bad sample counts (nsamples=%d burnin=%d Rcap=%d)", nsamples, burnin, Rcap);
-  VN_REQUIRE(rng->mode == VAENMF_RNG_DEVICE || (rng->eps && rng->u), "replay mode needs eps and u buffers");
+// the team chain of one MH-chain call, the mirror of chain.hip's vn_launch_wchain: kernel arguments from the plan and the
+// call, then the workgroup geometry
+int vn_launch_tchain(vaenmf_plan* p, const VnChainCall& cc, hipStream_t st) {
   ChainArgs a = {};
   a.dw = make_decw(p);
-  a.X2 = X2; a.W = W; a.Ht = Ht; a.g = g; a.B1 = B1; a.Z = Z; a.Zs = Zs; a.acc_out = acc_out; a.Vb = p->Vb_ext;
+  a.X2 = cc.X2; a.W = cc.W; a.Ht = cc.Ht; a.g = cc.g; a.B1 = cc.B1; a.Z = cc.Z; a.Zs = cc.Zs; a.acc_out = cc.acc_out; a.Vb = p->Vb_ext;
+  a.VsS = cc.VsS; a.src = cc.src; a.Rs = cc.Rs;
   a.tile_utt = p->d_tile_utt; a.tile_n0 = p->d_tile_n0; a.tile_cnt = p->d_tile_cnt; a.frame_off = p->d_frame_off;
-  a.utt_seed = p->d_utt_seed; a.eps = rng->eps; a.u = rng->u;
-  a.Fs = p->Fs; a.Kp = p->Kp; a.NT = p->NT; a.Rcap = Rcap; a.nsamples = nsamples; a.burnin = burnin;
-  a.rng_mode = rng->mode; a.call = rng->call; a.sd = sqrtf(var_rw); a.update_Z = update_Z;
-  hipStream_t st = (hipStream_t)stream;
+  a.utt_seed = p->d_utt_seed; a.eps = cc.eps; a.u = cc.u;
+  a.Fs = p->Fs; a.Kp = p->Kp; a.NT = p->NT; a.Rcap = cc.Rcap; a.nsamples = cc.nsamples; a.burnin = cc.burnin;
+  a.rng_mode = cc.rng_mode; a.call = cc.call; a.sd = cc.sd; a.update_Z = cc.update_Z;
   const bool split = p->cfg.precision == VAENMF_PREC_BF16X3;
-  p->store_R = p->store_Rs = 0;
-  size_t vss_bytes = 0;
-  if (p->store_on) {                                    // sample-variance store: sized by vaenmf_sample_store, never here
-    const int Rs = nsamples + 1;
-    const size_t esz = split ? sizeof(float) : sizeof(__bf16);
-    const size_t need_v = (size_t)(p->NT + 1) * Rs * p->Fs * esz, need_s = (size_t)p->NT * Rs;   // + a spare block (idle lanes)
-    VN_REQUIRE(need_v < 0xE0000000ull, "sample store: %d frames x %d slots x %d bins exceeds the 32-bit byte offsets of "
-               "the chain kernel; bind a smaller batch or switch the store off", p->NT, Rs, p->Fs);
-    VN_REQUIRE(need_v <= p->VsS_cap && need_s <= p->src_cap, "sample store too small for %d frames x %d samples: call "
-               "vaenmf_sample_store(plan, max_samples) after vaenmf_bind_batch (no allocation happens in vaenmf_mh_chain)", p->NT, nsamples);
-    a.VsS = p->VsS; a.src = p->src; a.Rs = Rs;
-    vss_bytes = need_v;
-  }
-  VnChainCall cc = {};
-  cc.X2 = X2; cc.W = W; cc.Ht = Ht; cc.g = g; cc.B1 = B1; cc.Z = Z; cc.Zs = Zs; cc.acc_out = acc_out;
-  cc.eps = rng->eps; cc.u = rng->u; cc.VsS = a.VsS; cc.VsS_bytes = vss_bytes; cc.src = a.src; cc.Rs = a.Rs;
-  cc.Rcap = Rcap; cc.nsamples = nsamples; cc.burnin = burnin; cc.rng_mode = rng->mode; cc.update_Z = update_Z;
-  cc.call = rng->call; cc.sd = a.sd; cc.sd_hi = p->Lz > 16 ? a.sd : 0.f; cc.one_hidden = p->one_hidden ? 1 : 0;
-  // wave-private chains (chain.hip) while every buffer of the batch is within their 32-bit byte offsets; a larger batch
-  // (about 300 k frames at 105 samples) runs the team kernel below, which addresses with 64 bits
-  if (vn_wchain_supported(p) && vn_wchain_fits(p, cc)) {
-    ProfScope ps(p, VN_K_CHAIN, st);
-    if (int e = vn_launch_wchain(p, cc, st)) return e;
-    if (p->store_on) { p->store_R = nsamples; p->store_Rs = nsamples + 1; }
-    return 0;
-  }
-  VN_REQUIRE(Zs != nullptr, "vaenmf_mh_chain: Zs may be NULL only where the wave-private chain kernels run (vaenmf_wchain_addressable)");
-  ProfScope ps(p, VN_K_CHAIN, st);
   int lrc = 0;
   switch (p->geom) {
     case 0: lrc = split ? launch_chain<4, 2, 5, true>(a, p->n_tiles, st) : launch_chain<4, 2, 5, false>(a, p->n_tiles, st); break;
@@ -1477,62 +1413,6 @@ extern "C" int vaenmf_mh_chain(vaenmf_plan* p, const float* X2, const float* W, 
     default: lrc = split ? launch_chain<8, 1, 5, true>(a, p->n_tiles, st) : launch_chain<8, 1, 5, false>(a, p->n_tiles, st); break;
   }
   if (lrc) return lrc;
-  VN_CHECK_HIP(hipGetLastError());
-  p->last_chain_kernel = 0;
-  if (p->store_on) { p->store_R = nsamples; p->store_Rs = nsamples + 1; }
-  return 0;
-}
-
-// max_samples > 0: switch the store on and size it for chains of up to max_samples samples per frame over the
-// plan's frame capacity (an allocating call, like vaenmf_plan_create); 0: off (the memory is kept).
-extern "C" int vaenmf_sample_store(vaenmf_plan* p, int32_t max_samples) {
-  VN_REQUIRE(p != nullptr, "null plan");
-  VN_REQUIRE(max_samples >= 0, "max_samples = %d", max_samples);
-  p->store_R = p->store_Rs = 0;
-  p->store_on = max_samples > 0;
-  if (!p->store_on) return 0;
-  const size_t esz = p->cfg.precision == VAENMF_PREC_BF16X3 ? sizeof(float) : sizeof(__bf16);
-  // sized for the bound batch (or, before a batch is bound, for the plan's frame capacity)
-  const size_t frames = (size_t)(p->NT > 0 ? p->NT : p->cfg.max_frames) + 1, Rs = (size_t)max_samples + 1;
-  size_t need_v = frames * Rs * p->Fs * esz, need_s = frames * Rs;
-  if (need_v >= 0xE0000000ull) need_v = 0xE0000000ull - 16;    // larger batches fall back to decoding (vaenmf_em_run); offsets from 0xF0000000 mark idle lanes
-  if (need_v > p->VsS_cap) {
-    if (p->VsS) VN_CHECK_HIP(hipFree(p->VsS));
-    p->VsS = nullptr; p->VsS_cap = 0;
-    VN_CHECK_HIP(hipMalloc(&p->VsS, need_v));
-    ++g_vn_dev_allocs;
-    p->VsS_cap = need_v;
-  }
-  if (need_s > p->src_cap) {
-    if (p->src) VN_CHECK_HIP(hipFree(p->src));
-    p->src = nullptr; p->src_cap = 0;
-    VN_CHECK_HIP(hipMalloc(&p->src, need_s * sizeof(int32_t)));
-    ++g_vn_dev_allocs;
-    p->src_cap = need_s;
-  }
-  p->Rcap_store = max_samples;
-  return 0;
-}
-
-namespace {
-template <typename ST>
-__global__ void store_gather_kernel(const ST* __restrict__ VsS, const int32_t* __restrict__ src, int NT, int R, int Rs, int Fs,
-                                    float* __restrict__ out) {
-  const int n = blockIdx.x / R, r = blockIdx.x - n * R;
-  const ST* row = VsS + ((size_t)n * Rs + src[(size_t)r * NT + n]) * Fs;
-  for (int f = threadIdx.x; f < Fs; f += blockDim.x) out[((size_t)n * R + r) * Fs + f] = (float)row[f];
-}
-}  // namespace
-
-extern "C" int vaenmf_sample_store_gather(vaenmf_plan* p, float* Vs_out, void* stream) {
-  VN_REQUIRE(p != nullptr && p->store_R > 0, "the sample store is empty (vaenmf_sample_store(plan, 1), then vaenmf_mh_chain)");
-  VN_REQUIRE(Vs_out != nullptr, "null output");
-  if (p->cfg.precision == VAENMF_PREC_BF16X3)
-    hipLaunchKernelGGL(store_gather_kernel<float>, dim3((unsigned)(p->NT * p->store_R)), dim3(64), 0, (hipStream_t)stream,
-                       reinterpret_cast<const float*>(p->VsS), p->src, p->NT, p->store_R, p->store_Rs, p->Fs, Vs_out);
-  else
-    hipLaunchKernelGGL(store_gather_kernel<__bf16>, dim3((unsigned)(p->NT * p->store_R)), dim3(64), 0, (hipStream_t)stream,
-                       reinterpret_cast<const __bf16*>(p->VsS), p->src, p->NT, p->store_R, p->store_Rs, p->Fs, Vs_out);
   VN_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -1589,128 +1469,6 @@ extern "C" int vaenmf_wiener(vaenmf_plan* p, const float* X2, const float* W, co
   return 0;
 }
 
-// the body of vaenmf_em_run: every launch on `stream`
-static int em_run_body(vaenmf_plan* p, const float* X2, float* W, float* Ht, float* g, float* Z, const float* B1, float* Zs,
-                       int32_t Rcap, int32_t niter, int32_t nsE, int32_t biE, int32_t nsWF, int32_t biWF, float var_rw,
-                       const float* X, float* S_hat, float* N_hat, double* cost, bool stored, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  vaenmf_rng rng = {VAENMF_RNG_DEVICE, 0, nullptr, nullptr};
-  // the per-frame cost sums of VN_COST_CHUNK iterations are kept (one row of the plan's cost buffer each) and reduced to
-  // cost[u][it] by ONE launch per chunk instead of one per iteration
-  const size_t cstride = (size_t)p->cfg.max_frames;
-  // With the sample-variance store on, the M-step never looks at the E-step's latent samples: the wave-private chain kernels
-  // then do not record them (Zs = NULL: 123 MB of writes per launch at the bench shape that nothing reads); the Wiener chain
-  // below records its own, which is what Zs holds after the reference's run() too (mcem.py:173, :477-482).
-  float* Zs_e = (stored && !vn_switches().keep_zs && vn_wchain_supported(p) &&
-                 vaenmf_wchain_addressable(p->NT, Rcap, nsE + biE, p->Fs, p->Kp, p->n_utt, 0)) ? nullptr : Zs;
-  for (int it = 0; it < niter; ++it) {                  // EM.run, mcem.py:159-165
-    rng.call = (uint32_t)it;
-    double* cf = p->cost_frames + (size_t)(it % VN_COST_CHUNK) * cstride;
-    if (int e = vaenmf_mh_chain(p, X2, W, Ht, g, Z, 1, B1, Zs_e, Rcap, nsE, biE, var_rw, &rng, nullptr, stream)) return e;
-    if (int e = stored ? vaenmf_m_step_stored(p, X2, W, Ht, g, cf, stream)
-                       : vaenmf_m_step(p, X2, W, Ht, g, Zs, Rcap, nsE, B1, cf, stream)) return e;
-    if (cost && ((it + 1) % VN_COST_CHUNK == 0 || it + 1 == niter)) {
-      const int it0 = it - it % VN_COST_CHUNK;
-      if (int e2 = vn_launch_cost_reduce(p, p->cost_frames, cstride, it - it0 + 1, nsE, cost, niter, it0, st)) return e2;
-    }
-  }
-  rng.call = (uint32_t)niter;                           // compute_WF(sample=True), mcem.py:173
-  if (int e = vaenmf_mh_chain(p, X2, W, Ht, g, Z, 0, B1, Zs, Rcap, nsWF, biWF, var_rw, &rng, nullptr, stream)) return e;
-  if (stored) return vaenmf_wiener_stored(p, W, Ht, g, X, S_hat, N_hat, nullptr, nullptr, stream);
-  return vaenmf_wiener(p, X2, W, Ht, g, Zs, Rcap, nsWF, B1, X, S_hat, N_hat, nullptr, nullptr, stream);
-}
-
-extern "C" int vaenmf_em_run(vaenmf_plan* p, const float* X2, float* W, float* Ht, float* g, float* Z, const float* B1,
-                             float* Zs, int32_t Rcap, int32_t niter, int32_t nsE, int32_t biE, int32_t nsWF, int32_t biWF,
-                             float var_rw, const float* X, float* S_hat, float* N_hat, double* cost, void* stream) {
-  if (int e = check_bound(p)) return e;
-  VN_REQUIRE(nsE <= Rcap && nsWF <= Rcap, "Rcap=%d too small for nsE=%d / nsWF=%d", Rcap, nsE, nsWF);
-  hipStream_t st = (hipStream_t)stream;
-  // with the sample store on (vaenmf_sample_store), the chain leaves the samples' variances in HBM and the
-  // M-step / Wiener filter stream them; otherwise they decode Zs again
-  // (a batch too large for the store's 32-bit element offsets decodes; every F the plan accepts, <= 640, is in the streaming
-  // kernels' bin range)
-  const size_t esz = p->cfg.precision == VAENMF_PREC_BF16X3 ? sizeof(float) : sizeof(__bf16);
-  auto fits = [&](int ns) { return (size_t)(p->NT + 1) * (ns + 1) * p->Fs * esz < 0xE0000000ull; };
-  const bool want = p->store_on, stored = want && fits(nsE) && fits(nsWF);
-  p->store_on = stored;
-  p->last_m_step_path = stored ? 1 : 2;               // VAENMF_Q_MSTEP_PATH: the caller can see a fall back to decoding
-  struct Restore { vaenmf_plan* p; bool v; ~Restore() { p->store_on = v; } } restore{p, want};
-  auto eager = [&]() { return em_run_body(p, X2, W, Ht, g, Z, B1, Zs, Rcap, niter, nsE, biE, nsWF, biWF, var_rw, X, S_hat, N_hat, cost, stored, stream); };
-
-  // ---- HIP graph of the whole call.  The kernels' arguments are values and device pointers; a signature (buffers,
-  // shapes, counts) is captured at its second appearance and replayed from then on (a few signatures are kept).  Contents that
-  // change from batch to batch -- spectrogram, seeds, frame tables -- live behind those pointers and are read at run time.
-  static const bool graphs_on = []() { const char* e = getenv("VAENMF_GRAPH"); return !(e && e[0] == '0'); }();
-  p->last_em_graph = 0;
-  if (!graphs_on || p->g_off || p->prof_on) return eager();
-  auto u64 = [](const void* q) { return (uint64_t)(uintptr_t)q; };
-  uint32_t vbits;
-  memcpy(&vbits, &var_rw, 4);
-  const VnSwitches sw = vn_switches();                  // kernel choices the captured launches depend on
-  uint64_t fo_hash = 1469598103934665603ull;            // the batch's frame offsets (FNV-1a): launches derive grids and chunk tables from them
-  for (int32_t v : p->h_frame_off) { fo_hash ^= (uint64_t)(uint32_t)v; fo_hash *= 1099511628211ull; }
-  const std::vector<uint64_t> key = {fo_hash,
-      u64(X2), u64(W), u64(Ht), u64(g), u64(Z), u64(B1), u64(Zs), u64(X), u64(S_hat), u64(N_hat), u64(cost),
-      (uint64_t)Rcap, (uint64_t)niter, (uint64_t)nsE, (uint64_t)biE, (uint64_t)nsWF, (uint64_t)biWF, (uint64_t)vbits, (uint64_t)stored,
-      (uint64_t)p->NT, (uint64_t)p->n_utt, (uint64_t)p->n_wtiles, (uint64_t)p->n_tiles, u64(p->VsS), u64(p->src), u64(p->Vb_ext),
-      (uint64_t)p->VsS_cap, (uint64_t)p->Rcap_store, u64(p->w1f), u64(p->w2f), u64(p->w3f), u64(p->w3c), u64(p->b3c), u64(p->b1),
-      u64(p->d_wt_utt), u64(p->d_wt_n0), u64(p->d_wt_cnt), u64(p->d_frame_off), u64(p->d_frame_utt), u64(p->d_frame_loc), u64(p->d_tile_utt),
-      u64(p->d_tile_n0), u64(p->d_tile_cnt), u64(p->d_utt_seed), u64(p->A1), u64(p->P), u64(p->normW), u64(p->wpart), u64(p->cost_frames), u64(p->w3n), u64(p->w1y), u64(p->b2), u64(p->b3),
-      u64(p->wpart64), u64(p->wpart16), u64(p->d_t64_n0), u64(p->d_t64_cnt), u64(p->d_t64_first), u64(p->d_t64_g0), (uint64_t)p->n_t64,
-      (uint64_t)p->cfg.precision, (uint64_t)p->cfg.K, (uint64_t)p->cfg.F,
-      (uint64_t)sw.wchain4, (uint64_t)sw.team_chain, (uint64_t)sw.wfused, (uint64_t)sw.wgroup, (uint64_t)(uint32_t)sw.wfused_grid,
-      (uint64_t)sw.keep_zs};
-  auto after_replay = [&](const vaenmf_plan::EmGraph& gph) {      // the host-side state an eager call leaves behind
-    if (stored) { p->store_R = nsWF; p->store_Rs = nsWF + 1; }
-    p->last_chain_kernel = gph.chain_kernel;
-    p->last_w_fused = gph.w_fused;
-  };
-  constexpr size_t MAX_GRAPHS = 4, MAX_SEEN = 8;
-  for (auto& gph : p->g_cache)
-    if (gph.key == key) {
-      VN_CHECK_HIP(hipGraphLaunch(gph.exec, st));
-      gph.used = ++p->g_tick;
-      after_replay(gph);
-      p->last_em_graph = 1;
-      return 0;
-    }
-  bool seen = false;
-  for (auto& k : p->g_seen) seen = seen || k == key;
-  if (!seen) {                                          // first call of this signature: eager (it also sets every kernel attribute)
-    if (p->g_seen.size() >= MAX_SEEN) p->g_seen.erase(p->g_seen.begin());
-    p->g_seen.push_back(key);
-    return eager();
-  }
-  // second appearance of the signature: capture
-  if (!p->cap_stream && hipStreamCreateWithFlags(&p->cap_stream, hipStreamNonBlocking) != hipSuccess) { p->g_off = true; return eager(); }
-  hipGraph_t graph = nullptr;
-  if (hipStreamBeginCapture(p->cap_stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); p->g_off = true; return eager(); }
-  const int rc = em_run_body(p, X2, W, Ht, g, Z, B1, Zs, Rcap, niter, nsE, biE, nsWF, biWF, var_rw, X, S_hat, N_hat, cost, stored, (void*)p->cap_stream);
-  const hipError_t ec = hipStreamEndCapture(p->cap_stream, &graph);
-  if (rc != 0 || ec != hipSuccess || !graph) {
-    if (graph) (void)hipGraphDestroy(graph);
-    (void)hipGetLastError();
-    p->g_off = true;
-    return eager();
-  }
-  hipGraphExec_t exec = nullptr;
-  const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(graph);
-  if (ei != hipSuccess || !exec) { (void)hipGetLastError(); p->g_off = true; return eager(); }
-  if (p->g_cache.size() >= MAX_GRAPHS) {                // evict the least recently used
-    size_t lru = 0;
-    for (size_t i = 1; i < p->g_cache.size(); ++i) if (p->g_cache[i].used < p->g_cache[lru].used) lru = i;
-    (void)hipGraphExecDestroy(p->g_cache[lru].exec);
-    p->g_cache.erase(p->g_cache.begin() + lru);
-  }
-  p->g_cache.push_back({key, exec, ++p->g_tick, p->last_chain_kernel, p->last_w_fused});
-  VN_CHECK_HIP(hipGraphLaunch(exec, st));
-  after_replay(p->g_cache.back());
-  p->last_em_graph = 1;
-  return 0;
-}
-
 #ifdef VN_STAMP
 extern "C" int vaenmf_debug_stamps(long long* out64, int reset) {
   long long h[64];
@@ -1720,9 +1478,3 @@ extern "C" int vaenmf_debug_stamps(long long* out64, int reset) {
   return 0;
 }
 #endif
-
-extern "C" int vaenmf_set_noise_psd(vaenmf_plan* p, const float* Vb) {
-  VN_REQUIRE(p != nullptr, "null plan");
-  p->Vb_ext = Vb;
-  return 0;
-}

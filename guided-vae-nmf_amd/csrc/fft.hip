@@ -1,6 +1,7 @@
-// Any-length STFT / iSTFT (python/processing/stft.py -> librosa.core.stft / istft) for every n_fft in [16, 4096] and the
-// options the power-of-two kernels of aux.hip do not take (any analysis / synthesis window, center=False, constant
-// padding).  Two FFT plans, both fp64 in LDS, one workgroup per frame:
+// STFT / iSTFT (python/processing/stft.py -> librosa.core.stft / istft) for every n_fft in [16, 4096], fp64 in LDS, one
+// workgroup per frame.  The reference's own settings at a power-of-two n_fft <= 2048 run the radix-2 kernels; every other
+// length and the options those do not take (any analysis / synthesis window, center=False, constant padding) run one of
+// two table-driven FFT plans:
 //   * mixed radix (n = 2^a 3^b 5^c 7^d): Stockham autosort stages of radix 4, 2, 3, 5, 7 ping-ponging between two LDS
 //     buffers of n complex doubles (32 n bytes, 128 KiB at n = 4096); twiddles exp(-2 pi i t / n) from a global table.
 //   * Bluestein (chirp-z, every other n): X[k] = w[k] sum_t (x[t] w[t]) conj(w[k-t]), w[t] = exp(-pi i t^2 / n), as a
@@ -13,14 +14,10 @@
 #include <utility>
 #include <vector>
 #include "common.h"
-#include "fft_lds.h"
-
-int vn_ensure_dyn_lds(const void* fn, int bytes);     // plan.hip
 
 namespace {
 
 constexpr int FFT_MIN = 16, FFT_MAX = 4096;
-constexpr int FFT_LDS_LIMIT = 160 * 1024;
 
 // Device tables of one transform size (pointers into one allocation; unused ones are null)
 struct FftPlan {
@@ -65,6 +62,127 @@ __device__ __forceinline__ double2 hermitian_bin(const float2* __restrict__ row,
   double vi = k <= half ? (double)v.y : -(double)v.y;
   if (k == 0 || 2 * k == nfft) vi = 0.0;
   return make_double2((double)v.x, vi);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Radix-2 FFT in LDS, shared by the power-of-two STFT kernels and the Bluestein convolution
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int bitrev(int x, int bits) { return (int)(__brev((unsigned)x) >> (32 - bits)); }
+
+// in-place complex FFT of length n (power of two) on LDS arrays; sign = -1 forward, +1 inverse
+__device__ void fft_lds(double* re, double* im, const double* twr, const double* twi, int n, int bits, int sign) {
+  for (int len = 2, st = n >> 1, lh = 0; len <= n; len <<= 1, st >>= 1, ++lh) {
+    const int half = len >> 1;                     // = 1 << lh
+    for (int b = threadIdx.x; b < (n >> 1); b += blockDim.x) {
+      const int grp = b >> lh, pos = b & (half - 1);
+      const int i0 = grp * len + pos, i1 = i0 + half;
+      const double wr = twr[pos * st], wi = sign * twi[pos * st];
+      const double xr = re[i1] * wr - im[i1] * wi, xi = re[i1] * wi + im[i1] * wr;
+      re[i1] = re[i0] - xr; im[i1] = im[i0] - xi;
+      re[i0] += xr;         im[i0] += xi;
+    }
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Radix-2 path (power-of-two n_fft <= 2048, Hann window, center, reflect padding): radix-2 FFT in LDS, fp64; twiddles and
+// window from device sincospi, overlap-add sums in float.  Its output bits differ from the table-driven kernels below.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ wav, const int64_t* __restrict__ samp_off,
+                                                   const int32_t* __restrict__ frame_off, const int32_t* __restrict__ frame_utt,
+                                                   const int32_t* __restrict__ pad_len, int nfft, int bits, int hop, int Fs,
+                                                   float2* __restrict__ X) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  double* re = reinterpret_cast<double*>(smem);
+  double* im = re + nfft;
+  double* twr = im + nfft;
+  double* twi = twr + nfft / 2;
+  const int n = blockIdx.x, u = frame_utt[n], i = n - frame_off[u];
+  const int64_t off = samp_off[u];
+  const int64_t T = samp_off[u + 1] - off;
+  const int64_t Tp = pad_len[u];                 // length after the end-pad rule (stft.py:48-53)
+  for (int t = threadIdx.x; t < nfft / 2; t += blockDim.x) {
+    double s, c;
+    sincospi(-2.0 * t / nfft, &s, &c);           // exp(-2 pi i t / nfft)
+    twr[t] = c; twi[t] = s;
+  }
+  __syncthreads();
+  for (int t = threadIdx.x; t < nfft; t += blockDim.x) {
+    int64_t p = (int64_t)i * hop + t - nfft / 2;  // centre=True, reflect padding
+    if (p < 0) p = -p;
+    if (p >= Tp) p = 2 * (Tp - 1) - p;
+    const double v = (p >= 0 && p < T) ? (double)wav[off + p] : 0.0;
+    // cos(2 pi t / nfft) from the twiddle table (two thirds of this kernel's time went into a second fp64 sincospi per sample)
+    const double cw = t < nfft / 2 ? twr[t] : -twr[t - nfft / 2];
+    const int r = bitrev(t, bits);
+    re[r] = v * (0.5 - 0.5 * cw);                 // periodic Hann
+    im[r] = 0.0;
+  }
+  __syncthreads();
+  fft_lds(re, im, twr, twi, nfft, bits, 1);       // table holds exp(-i..): sign +1 keeps it
+  const int F = nfft / 2 + 1;
+  for (int f = threadIdx.x; f < Fs; f += blockDim.x)
+    X[(size_t)n * Fs + f] = f < F ? make_float2((float)re[f], (float)im[f]) : make_float2(0.f, 0.f);
+}
+
+__global__ __launch_bounds__(256) void istft_frames_kernel(const float2* __restrict__ S, int nfft, int bits, int Fs,
+                                                           float* __restrict__ work) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  double* re = reinterpret_cast<double*>(smem);
+  double* im = re + nfft;
+  double* twr = im + nfft;
+  double* twi = twr + nfft / 2;
+  const int n = blockIdx.x;
+  for (int t = threadIdx.x; t < nfft / 2; t += blockDim.x) {
+    double s, c;
+    sincospi(2.0 * t / nfft, &s, &c);             // exp(+2 pi i t / nfft)
+    twr[t] = c; twi[t] = s;
+  }
+  const int half = nfft / 2;
+  for (int k = threadIdx.x; k < nfft; k += blockDim.x) {
+    const int kk = k <= half ? k : nfft - k;
+    const float2 v = S[(size_t)n * Fs + kk];
+    double vr = v.x, vi = (k <= half) ? v.y : -v.y;
+    if (k == 0 || k == half) vi = 0.0;            // c2r ignores the imaginary part of DC / Nyquist
+    const int r = bitrev(k, bits);
+    re[r] = vr; im[r] = vi;
+  }
+  __syncthreads();
+  fft_lds(re, im, twr, twi, nfft, bits, 1);
+  for (int t = threadIdx.x; t < nfft; t += blockDim.x) {
+    const double cw = t < nfft / 2 ? twr[t] : -twr[t - nfft / 2];     // cos(2 pi t / nfft), see stft_kernel
+    work[(size_t)n * nfft + t] = (float)(re[t] / nfft * (0.5 - 0.5 * cw));
+  }
+}
+
+__global__ void istft_ola_kernel(const float* __restrict__ work, const int64_t* __restrict__ samp_off,
+                                 const int32_t* __restrict__ frame_off, int n_utt, int nfft, int hop,
+                                 float* __restrict__ out) {
+  const int u = blockIdx.y;
+  const int64_t off = samp_off[u], T = samp_off[u + 1] - off;
+  const int nb = frame_off[u], nfr = frame_off[u + 1] - nb;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < T; t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t p = t + nfft / 2;
+    float y = 0.f;
+    double wss = 0.0;
+    if (p < (int64_t)nfft + (int64_t)hop * (nfr - 1)) {
+      int64_t i_lo = (p - nfft + hop) / hop;        // ceil((p - nfft + 1)/hop)
+      if (p - nfft + 1 <= 0) i_lo = 0;
+      int64_t i_hi = p / hop;
+      if (i_hi > nfr - 1) i_hi = nfr - 1;
+      for (int64_t i = i_lo; i <= i_hi; ++i) {
+        const int tt = (int)(p - i * hop);
+        double sw, cw;
+        sincospi(2.0 * tt / nfft, &sw, &cw);
+        const double wv = 0.5 - 0.5 * cw;
+        y += work[(size_t)(nb + i) * nfft + tt];
+        wss += wv * wv;
+      }
+      if (wss > 1.1754943508222875e-38) y = (float)(y / wss);
+    }
+    out[off + t] = y;
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -403,8 +521,11 @@ int get_plan(int n, FftPlan* out) {
 }
 
 size_t frame_lds(const FftPlan& P) { return P.m ? (size_t)16 * P.m : (size_t)32 * P.n; }
+size_t r2_lds(int nfft) { return (size_t)nfft * 3 * sizeof(double); }      // radix-2 kernels: re, im, twiddles
+int ilog2(int n) { int b = 0; while ((1 << b) < n) ++b; return b; }
 
-bool legacy_path(const vaenmf_stft_opts* o) {
+// the radix-2 kernels take the reference's own settings at power-of-two lengths
+bool radix2_path(const vaenmf_stft_opts* o) {
   return o->nfft <= 2048 && (o->nfft & (o->nfft - 1)) == 0 && o->window == nullptr && o->center && o->pad_mode == VAENMF_PAD_REFLECT;
 }
 
@@ -449,16 +570,20 @@ extern "C" int vaenmf_stft_batch_ex(const float* wav, int32_t n_frames_total, co
   VN_REQUIRE(wav && X && n_frames_total > 0 && sample_offsets && frame_offsets && frame_utt && padded_len,
              "vaenmf_stft_batch_ex: bad arguments");
   if (int rc = check_opts(opts, Fs, "vaenmf_stft_batch_ex")) return rc;
-  if (legacy_path(opts))
-    return vaenmf_stft_batch(wav, n_frames_total, sample_offsets, frame_offsets, frame_utt, padded_len, opts->nfft, opts->hop, Fs, X, stream);
+  hipStream_t st = (hipStream_t)stream;
+  if (radix2_path(opts)) {
+    hipLaunchKernelGGL(stft_kernel, dim3(n_frames_total), dim3(256), r2_lds(opts->nfft), st, wav, sample_offsets, frame_offsets,
+                       frame_utt, padded_len, opts->nfft, ilog2(opts->nfft), opts->hop, Fs, reinterpret_cast<float2*>(X));
+    VN_CHECK_HIP(hipGetLastError());
+    return 0;
+  }
   FftPlan P;
   if (int rc = get_plan(opts->nfft, &P)) return rc;
   const FrameArgs a{opts->nfft, opts->hop, Fs, opts->center ? 1 : 0, opts->pad_mode == VAENMF_PAD_REFLECT ? 1 : 0,
                     opts->window ? opts->window : P.hann};
   const size_t lds = frame_lds(P);
   const void* fn = P.m ? (const void*)stft_bs_kernel : (const void*)stft_mr_kernel;
-  if (int e = vn_ensure_dyn_lds(fn, FFT_LDS_LIMIT)) return e;
-  hipStream_t st = (hipStream_t)stream;
+  if (int e = vn_ensure_dyn_lds(fn, VN_LDS_LIMIT)) return e;
   if (P.m)
     hipLaunchKernelGGL(stft_bs_kernel, dim3(n_frames_total), dim3(256), lds, st, wav, sample_offsets, frame_offsets, frame_utt,
                        padded_len, a, P, reinterpret_cast<float2*>(X));
@@ -475,16 +600,21 @@ extern "C" int vaenmf_istft_batch_ex(const float* S, int32_t n_utt, int32_t n_fr
   VN_REQUIRE(S && work && wav_out && n_utt > 0 && n_frames_total > 0 && sample_offsets && frame_offsets,
              "vaenmf_istft_batch_ex: bad arguments");
   if (int rc = check_opts(opts, Fs, "vaenmf_istft_batch_ex")) return rc;
-  if (legacy_path(opts))
-    return vaenmf_istft_batch(S, n_utt, n_frames_total, sample_offsets, frame_offsets, opts->nfft, opts->hop, Fs, work, wav_out, stream);
+  hipStream_t st = (hipStream_t)stream;
+  const float2* S2 = reinterpret_cast<const float2*>(S);
+  if (radix2_path(opts)) {
+    hipLaunchKernelGGL(istft_frames_kernel, dim3(n_frames_total), dim3(256), r2_lds(opts->nfft), st, S2, opts->nfft, ilog2(opts->nfft), Fs, work);
+    hipLaunchKernelGGL(istft_ola_kernel, dim3(64, n_utt), dim3(256), 0, st, work, sample_offsets, frame_offsets, n_utt, opts->nfft,
+                       opts->hop, wav_out);
+    VN_CHECK_HIP(hipGetLastError());
+    return 0;
+  }
   FftPlan P;
   if (int rc = get_plan(opts->nfft, &P)) return rc;
   const FrameArgs a{opts->nfft, opts->hop, Fs, opts->center ? 1 : 0, 0, opts->window ? opts->window : P.hann};
   const size_t lds = frame_lds(P);
   const void* fn = P.m ? (const void*)istft_bs_frames_kernel : (const void*)istft_mr_frames_kernel;
-  if (int e = vn_ensure_dyn_lds(fn, FFT_LDS_LIMIT)) return e;
-  hipStream_t st = (hipStream_t)stream;
-  const float2* S2 = reinterpret_cast<const float2*>(S);
+  if (int e = vn_ensure_dyn_lds(fn, VN_LDS_LIMIT)) return e;
   if (P.m)
     hipLaunchKernelGGL(istft_bs_frames_kernel, dim3(n_frames_total), dim3(256), lds, st, S2, a, P, work);
   else

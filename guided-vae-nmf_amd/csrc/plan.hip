@@ -196,8 +196,7 @@ extern "C" void vaenmf_plan_destroy(vaenmf_plan* p) {
   for (void* q : ptrs)
     if (q) (void)hipFree(q);
   for (hipEvent_t e : p->prof_ev) (void)hipEventDestroy(e);
-  for (auto& gph : p->g_cache) if (gph.exec) (void)hipGraphExecDestroy(gph.exec);
-  if (p->cap_stream) (void)hipStreamDestroy(p->cap_stream);
+  p->graphs.release();
   if (p->h_seed_ring) (void)hipHostFree(p->h_seed_ring);
   for (int i = 0; i < vaenmf_plan::SEED_RING; ++i) if (p->seed_ev[i]) (void)hipEventDestroy(p->seed_ev[i]);
   delete p;
@@ -213,7 +212,7 @@ extern "C" int vaenmf_plan_query(const vaenmf_plan* p, int32_t what) {
     case VAENMF_Q_NUTT: return p->n_utt;
     case VAENMF_Q_MSTEP_PATH: return p->last_m_step_path;
     case VAENMF_Q_WTILES: return p->n_wtiles;
-    case VAENMF_Q_EM_GRAPH: return p->last_em_graph;
+    case VAENMF_Q_EM_GRAPH: return p->graphs.last;
     case VAENMF_Q_DEV_ALLOCS: return (int)g_vn_dev_allocs;
     case VAENMF_Q_W_FUSED: return p->last_w_fused;
     case VAENMF_Q_CHAIN_KERNEL: return p->last_chain_kernel;

@@ -16,8 +16,6 @@
 // element that every lane computes redundantly (same address: a broadcast load).
 #include "common.h"
 
-int vn_ensure_dyn_lds(const void* fn, int bytes);     // plan.hip
-
 namespace {
 
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
@@ -1325,10 +1323,6 @@ int check_store(const vaenmf_plan* p) {
 }
 
 }  // namespace
-
-// aux.hip
-int vn_launch_w_update(const vaenmf_plan* p, float* W, const float* Ht, hipStream_t st);
-int vn_launch_w_update_tiles(const vaenmf_plan* p, float* W, hipStream_t st, bool groups);
 
 namespace {
 // W statistics + the W update's sums in one kernel: the bench shapes (bf16 rows, one 256-bin chunk, rank <= 8,

@@ -56,10 +56,7 @@ SIGNATURES = {
     "vaenmf_dense": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _I, _P]),
     "vaenmf_power_spec": (_I, [_P, _P, _I64, _P]),
     "vaenmf_stft_geometry": (_I, [_I64, _D, _D, _D, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
-    "vaenmf_stft_num_frames": (_I, [_I64, _D, _D, _D, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
-    "vaenmf_stft_batch": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "vaenmf_stft_batch_ex": (_I, [_P, _I, _P, _P, _P, _P, C.POINTER(StftOpts), _I, _P, _P]),
-    "vaenmf_istft_batch": (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
     "vaenmf_istft_batch_ex": (_I, [_P, _I, _I, _P, _P, C.POINTER(StftOpts), _I, _P, _P, _P]),
     "vaenmf_lorenz_work_bytes": (_I64, [_I, _I, _I, _I]),
     "vaenmf_lorenz_labels": (_I, [_P, _I, _P, _I, _I, _I, _F, _F, _F, _P, _I, _P, _P, _I64, _P]),

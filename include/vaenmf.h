@@ -230,12 +230,11 @@ int vaenmf_power_spec(const float* X, float* X2, int64_t n, void* stream);
  * (:48-53) on the host and returns n_fft, hop, the frame count and the padded length Tp
  * of one utterance: 1 + (Tp + 2*(n_fft/2) - n_fft)/hop frames with center (librosa pads
  * n_fft/2 samples on both sides), 1 + (Tp - n_fft)/hop without (fails when Tp < n_fft).
- * vaenmf_stft_num_frames is vaenmf_stft_geometry with center = 1.
- * vaenmf_stft_batch: wav DEV float [sum T]; sample_offsets DEV int64 [n_utt+1];
+ * vaenmf_stft_batch_ex: wav DEV float [sum T]; sample_offsets DEV int64 [n_utt+1];
  * frame_offsets DEV int32 [n_utt+1]; frame_utt DEV int32 [NT]; padded_len DEV int32
- * [n_utt]; X DEV complex64 [NT][Fs] (Fs >= n_fft/2+1, bins >= n_fft/2+1 zeroed);
- * periodic Hann, center, reflect padding.  vaenmf_stft_batch_ex takes the window, the
- * centring and the pad mode from `opts`.
+ * [n_utt]; X DEV complex64 [NT][Fs] (Fs >= n_fft/2+1, bins >= n_fft/2+1 zeroed); the
+ * window, the centring and the pad mode come from `opts` (the reference's own: periodic
+ * Hann, center, reflect padding).
  * Kernels: power-of-two n_fft <= 2048 with periodic Hann, center and reflect padding run
  * the radix-2 kernels; everything else a mixed-radix (radices 2, 3, 4, 5, 7) or, for
  * lengths with a prime factor above 7, a Bluestein FFT.  Per-size twiddle / chirp tables
@@ -253,12 +252,6 @@ typedef struct vaenmf_stft_opts {
 int vaenmf_stft_geometry(int64_t n_samples, double fs, double wlen_sec, double hop_percent,
                          int32_t center, int32_t* nfft, int32_t* hop, int32_t* n_frames,
                          int32_t* n_padded);
-int vaenmf_stft_num_frames(int64_t n_samples, double fs, double wlen_sec, double hop_percent,
-                           int32_t* nfft, int32_t* hop, int32_t* n_frames, int32_t* n_padded);
-int vaenmf_stft_batch(const float* wav, int32_t n_frames_total, const int64_t* sample_offsets,
-                      const int32_t* frame_offsets, const int32_t* frame_utt,
-                      const int32_t* padded_len, int32_t nfft, int32_t hop, int32_t Fs,
-                      float* X, void* stream);
 int vaenmf_stft_batch_ex(const float* wav, int32_t n_frames_total, const int64_t* sample_offsets,
                          const int32_t* frame_offsets, const int32_t* frame_utt,
                          const int32_t* padded_len, const vaenmf_stft_opts* opts, int32_t Fs,
@@ -268,12 +261,7 @@ int vaenmf_stft_batch_ex(const float* wav, int32_t n_frames_total, const int64_t
  * float [sum T] (T = sample_offsets[u+1]-sample_offsets[u] = max_len of utterance u;
  * samples past the last frame are zero); work DEV float [NT][nfft] scratch (the windowed
  * frames).  With center the first n_fft/2 samples of the overlap-add are dropped.
- * vaenmf_istft_batch: periodic Hann, center; vaenmf_istft_batch_ex: window and centring
- * from `opts` (pad_mode is not used). */
-int vaenmf_istft_batch(const float* S, int32_t n_utt, int32_t n_frames_total,
-                       const int64_t* sample_offsets, const int32_t* frame_offsets,
-                       int32_t nfft, int32_t hop, int32_t Fs, float* work, float* wav_out,
-                       void* stream);
+ * Window and centring come from `opts` (pad_mode is not used). */
 int vaenmf_istft_batch_ex(const float* S, int32_t n_utt, int32_t n_frames_total,
                           const int64_t* sample_offsets, const int32_t* frame_offsets,
                           const vaenmf_stft_opts* opts, int32_t Fs, float* work,

@@ -93,7 +93,7 @@ def test_windows_centring_and_pad_modes(n):
 
 def test_new_kernels_match_the_power_of_two_kernels():
     """An explicit periodic-Hann array forces the new kernels at 512 / 1024 points; the default call runs the radix-2
-    kernels of aux.hip."""
+    kernels of fft.hip."""
     need_gpu()
     from vaenmf import stft as vstft
     x = _speech()

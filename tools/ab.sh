@@ -1,6 +1,7 @@
 #!/bin/bash
 # dev aid (GPU box): time bench.py with several builds of the library in ONE call (box-to-box variance is +-3%)
 # usage: tools/ab.sh "<bench args>" tagA tagB ...   (tag "main" = libvaenmf.so)
+# a variant libvaenmf_<tag>.so comes from: VAENMF_HIPCC_FLAGS="<extra hipcc flags>" python __graft_entry__.py --tag <tag>
 args=$1; shift
 out=${AB_LOG_DIR:-$(mktemp -d)}; mkdir -p "$out"; echo "logs: $out"
 for t in "$@"; do

@@ -1,4 +1,5 @@
-"""dev aid: per-phase tick shares of wchain_kernel (workgroup 0, wave 0) from a -DVN_STAMP build (libvaenmf_dbg.so)."""
+"""dev aid: per-phase tick shares of wchain_kernel (workgroup 0, wave 0) from a -DVN_STAMP build (libvaenmf_dbg.so:
+VAENMF_HIPCC_FLAGS=-DVN_STAMP python __graft_entry__.py --tag dbg)."""
 import os, sys, ctypes as C
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "guided-vae-nmf_amd"))
