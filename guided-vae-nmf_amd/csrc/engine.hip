@@ -933,6 +933,10 @@ __global__ __launch_bounds__(NW * NTEAM * 64) void decode_kernel(const DecodeArg
         split8<SPLIT>(zz[0], zhi[0], zlo[0]);
         split8<SPLIT>(zz[1], zhi[1], zlo[1]);
       }
+      // bf16x3 mode: the two layer images alias, so layer 1 below overwrites what the previous call's output layer reads.
+      // Nothing else orders the two: a wavefront that owns fewer bin tiles than its neighbours (NT3 not a multiple of
+      // the team's wavefronts; every F = 16k+1 of a power-of-two STFT divides evenly) got here while they were reading.
+      if (M::ALIAS) d.team_sync();
       d.hidden(zhi, zlo, bias1, []() {});
       if (d.nyq) {
         const float bn = b3l[dw.F - 1];

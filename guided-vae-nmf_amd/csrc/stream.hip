@@ -14,6 +14,14 @@
 //
 // Bins of the odd last bin and the padding (f >= Fm: F-1 when F = 16k+1) are handled as one extra
 // element that every lane computes redundantly (same address: a broadcast load).
+//
+// Padding bins (f >= F).  A lane's chunk is valid as a whole when Fm is a multiple of 4 (every F = 16k+1 and every
+// multiple of 4).  Otherwise the chunk that holds bin Fm-1 is partly padding, where W = 0 and the stored variance
+// is 0 (or 2^-100), so Vx = 0 and 1/Vx = inf there.  The kernels that sum over bins or write per-bin results
+// (hg_stream, wf_stream) then run their TAIL instantiation: per-bin validity ok(c, t), Vb = 1 and X2 = 0 in the padding
+// (every intermediate finite), padding terms left out of every sum and written as exact zeros.  The W-statistics kernels
+// need none: their per-bin results A1 / P / partial sums are read back for f < F only (aux.hip).  TAIL is a template
+// argument so that the instantiations of the other shapes are the ones they were.
 #include "common.h"
 
 namespace {
@@ -52,12 +60,13 @@ __device__ __forceinline__ float wave_sum(float v) { return sum_rows4(sum_row16(
 // a value every lane holds alike, kept in a scalar register from here on
 __device__ __forceinline__ float vn_uniform(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); }
 
-template <int NCH, int KP, typename ST>
+template <int NCH, int KP, typename ST, bool TAIL = false>
 struct FrameCtx {
   const StreamArgs& a;
   int lane;
   bool cv[NCH];                // chunk c holds real bins for this lane
   int f0[NCH];
+  int nb[NCH];                 // TAIL: bins of chunk c below Fm (>= 4: the whole chunk)
   unsigned fo[NCH];            // cv ? f0 : 0 as an unsigned element offset: (uniform row pointer)[fo] is addressed as SGPR base + 32-bit
                                // VGPR offset, no 64-bit address pair per load in vector registers
   bool has_x;                  // an extra bin F-1 beside the 4-bin chunks
@@ -79,7 +88,10 @@ struct FrameCtx {
   __device__ FrameCtx(const StreamArgs& a_, float* wl_) : a(a_), wl(wl_) {
     lane = threadIdx.x & 63;
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) { f0[c] = 256 * c + 4 * lane; cv[c] = f0[c] < a.Fm; fo[c] = cv[c] ? (unsigned)f0[c] : 0u; }
+    for (int c = 0; c < NCH; ++c) {
+      f0[c] = 256 * c + 4 * lane; cv[c] = f0[c] < a.Fm; fo[c] = cv[c] ? (unsigned)f0[c] : 0u;
+      nb[c] = TAIL ? a.Fm - f0[c] : 0;
+    }
     has_x = a.F != a.Fm;
     wutt = -1;
     blk_utt = -1;
@@ -87,6 +99,17 @@ struct FrameCtx {
     wx = 0.f;
     nw = 1.f;
     in_lds = false;
+  }
+  // bin t of chunk c is a real bin (without TAIL: Fm is a multiple of 4 and the chunk is valid as a whole)
+  __device__ __forceinline__ bool ok(int c, int t) const { return TAIL ? t < nb[c] : cv[c]; }
+  // TAIL: the padding bins of a partly valid chunk get the values of an invalid one
+  __device__ __forceinline__ void pad_bins(f32x4 (&v)[NCH], float pad) const {
+    if constexpr (TAIL) {
+#pragma unroll
+      for (int c = 0; c < NCH; ++c)
+#pragma unroll
+        for (int t = 1; t < 4; ++t) v[c][t] = ok(c, t) ? v[c][t] : pad;
+    }
   }
   __device__ __forceinline__ float nwk(int k) const {
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, nw), k));
@@ -158,6 +181,7 @@ struct FrameCtx {
         }
         vb[c] = cv[c] ? v : f32x4{1.f, 1.f, 1.f, 1.f};
       }
+      pad_bins(vb, 1.f);
       vbx = 1.f;
       if (has_x) {
         float v = 0.f;
@@ -187,6 +211,7 @@ struct FrameCtx {
         }
       }
     }
+    pad_bins(vb, 1.f);
     vbx = 1.f;
     if (has_x) {
       float v = 0.f;
@@ -236,6 +261,7 @@ struct FrameCtx {
 #pragma unroll
     for (int c = 0; c < NCH; ++c)
       vb[c] = cv[c] ? *reinterpret_cast<const f32x4*>(row + fo[c]) : f32x4{1.f, 1.f, 1.f, 1.f};
+    pad_bins(vb, 1.f);
     vbx = has_x ? row[a.F - 1] : 1.f;
   }
   __device__ __forceinline__ void load_x2(int n, f32x4 (&x2)[NCH], float& x2x) const {
@@ -243,6 +269,7 @@ struct FrameCtx {
 #pragma unroll
     for (int c = 0; c < NCH; ++c)
       x2[c] = cv[c] ? *reinterpret_cast<const f32x4*>(row + fo[c]) : f32x4{0.f, 0.f, 0.f, 0.f};
+    pad_bins(x2, 0.f);
     x2x = has_x ? row[a.F - 1] : 0.f;
   }
   // write a per-bin result row (bins >= F zeroed)
@@ -506,10 +533,10 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1) ? ST_WAVES : 2) void wst
 }
 
 // RT > 0: exactly RT samples per frame (no per-row branch: 90 uniform branches per frame otherwise)
-template <int NCH, int KP, typename ST, int RT = 0>
+template <int NCH, int KP, typename ST, int RT = 0, bool TAIL = false>
 __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1 && sizeof(ST) == 2) ? ST_WAVES : 2) void hg_stream_kernel(const StreamArgs a) {
   extern __shared__ __attribute__((aligned(16))) float wlds[];
-  FrameCtx<NCH, KP, ST> fc(a, wlds + (KP <= 8 ? (size_t)(threadIdx.x >> 6) * a.Fs * KP : 0));
+  FrameCtx<NCH, KP, ST, TAIL> fc(a, wlds + (KP <= 8 ? (size_t)(threadIdx.x >> 6) * a.Fs * KP : 0));
   fc.stage_block_w();
   // (two chunks, rank <= 16: 0.306 -> 0.286 ms on the 1024-pt shape; at rank 32 the registers do not suffice: 0.535 -> 0.608,
   // and the whole-frame batch still spills, 288 bytes, and gains nothing)
@@ -581,8 +608,8 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1 && sizeof(ST) == 2) ? ST_
       for (int c = 0; c < NCH; ++c)
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-          a2[c][t] = fc.cv[c] ? a2[c][t] * x2[c][t] : 0.f;
-          a1[c][t] = fc.cv[c] ? a1[c][t] : 0.f;
+          a2[c][t] = fc.ok(c, t) ? a2[c][t] * x2[c][t] : 0.f;
+          a1[c][t] = fc.ok(c, t) ? a1[c][t] : 0.f;
         }
       const bool lead = fc.lane == 0 && fc.has_x;
       a2x = lead ? a2x * x2x : 0.f;
@@ -633,7 +660,8 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1 && sizeof(ST) == 2) ? ST_
       for (int c = 0; c < NCH; ++c)
         if (fc.cv[c]) {
 #pragma unroll
-          for (int t = 0; t < 4; ++t) { nu += x2[c][t] * ng[c][t]; de += dg[c][t]; }
+          for (int t = 0; t < 4; ++t)
+            if (!TAIL || fc.ok(c, t)) { nu += x2[c][t] * ng[c][t]; de += dg[c][t]; }
         }
       if (fc.lane == 0 && fc.has_x) { nu += x2x * ngx; de += dgx; }
       nu = wave_sum(nu);
@@ -685,7 +713,8 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1 && sizeof(ST) == 2) ? ST_
     for (int c = 0; c < NCH; ++c)
       if (fc.cv[c]) {
 #pragma unroll
-        for (int t = 0; t < 4; ++t) cs += cl[c][t] * LN2_F + x2[c][t] * cx[c][t];
+        for (int t = 0; t < 4; ++t)
+          if (!TAIL || fc.ok(c, t)) cs += cl[c][t] * LN2_F + x2[c][t] * cx[c][t];
       }
     if (fc.lane == 0 && fc.has_x) cs += clx * LN2_F + x2x * cxx;
     const double cd = sum_rows4_d((double)sum_row16(cs));     // rows in fp32 (DPP), then fp64 across the 4 rows
@@ -693,10 +722,10 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1 && sizeof(ST) == 2) ? ST_
   }
 }
 
-template <int NCH, int KP, typename ST>
+template <int NCH, int KP, typename ST, bool TAIL = false>
 __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1) ? ST_WAVES : 2) void wf_stream_kernel(const StreamArgs a) {
   extern __shared__ __attribute__((aligned(16))) float wlds[];
-  FrameCtx<NCH, KP, ST> fc(a, wlds + (KP <= 8 ? (size_t)(threadIdx.x >> 6) * a.Fs * KP : 0));
+  FrameCtx<NCH, KP, ST, TAIL> fc(a, wlds + (KP <= 8 ? (size_t)(threadIdx.x >> 6) * a.Fs * KP : 0));
   fc.stage_block_w();
   using RBt = RowBatch<NCH, ST>;
   int n_beg, n_end;
@@ -755,7 +784,7 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1) ? ST_WAVES : 2) void wf_
         const size_t o = (size_t)n * a.Fs + fc.f0[c];
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-          const float ms = ws[c][t] * invR, mn = wn[c][t] * invR;
+          const float ms = (!TAIL || fc.ok(c, t)) ? ws[c][t] * invR : 0.f, mn = (!TAIL || fc.ok(c, t)) ? wn[c][t] * invR : 0.f;
           const float xr = a.X[2 * (o + t)], xi = a.X[2 * (o + t) + 1];
           a.S_hat[2 * (o + t)] = ms * xr;  a.S_hat[2 * (o + t) + 1] = ms * xi;
           a.N_hat[2 * (o + t)] = mn * xr;  a.N_hat[2 * (o + t) + 1] = mn * xi;
@@ -1245,7 +1274,7 @@ StreamArgs base_args(const vaenmf_plan* p) {
 enum { SK_WSTATS, SK_HG, SK_WF };
 
 template <int KIND, int NCH, int KP, typename ST>
-int launch_st(StreamArgs a, int grid, hipStream_t st) {
+int launch_st(StreamArgs a, int grid, hipStream_t st, bool tail) {
   // rank <= 8: one W[utt] per wavefront; above: one per workgroup when it leaves room for two workgroups per CU
   const size_t one = (size_t)a.Fs * KP * sizeof(float);
   const size_t lds = KP <= 8 ? 4 * one : (one <= 72 * 1024 ? one : 0);
@@ -1268,6 +1297,7 @@ int launch_st(StreamArgs a, int grid, hipStream_t st) {
     }
     return go(wstats_stream_kernel<NCH, KP, ST>, grid);
   } else if constexpr (KIND == SK_HG) {
+    if (tail) return go(hg_stream_kernel<NCH, KP, ST, 0, true>, grid);      // Fm % 4 != 0: per-bin validity (FrameCtx)
     if constexpr (NCH == 1 && KP <= 8) {
       // exact-sample-count instantiations (one chunk, rank <= 8): no per-row branches, rows consumed as they arrive (precise
       // vmcnt counts): 0.198 -> 0.172 ms.  (Slower while the extra-bin addresses still spilled.)  (The rotating-register form
@@ -1282,13 +1312,15 @@ int launch_st(StreamArgs a, int grid, hipStream_t st) {
     }
     return go(hg_stream_kernel<NCH, KP, ST>, grid);
   } else {
+    if (tail) return go(wf_stream_kernel<NCH, KP, ST, true>, grid);
     return go(wf_stream_kernel<NCH, KP, ST>, grid);
   }
 }
 template <int KIND, int NCH, int KP>
 int launch_one(const StreamArgs& a, int grid, hipStream_t st) {
-  if (a.store_f32) return launch_st<KIND, NCH, KP, float>(a, grid, st);
-  return launch_st<KIND, NCH, KP, __bf16>(a, grid, st);
+  const bool tail = (a.Fm & 3) != 0;                    // the chunk that holds bin Fm-1 is partly padding
+  if (a.store_f32) return launch_st<KIND, NCH, KP, float>(a, grid, st, tail);
+  return launch_st<KIND, NCH, KP, __bf16>(a, grid, st, tail);
 }
 template <int KIND, int NCH>
 int launch_kp(const StreamArgs& a, int Kp, int grid, hipStream_t st) {

@@ -66,7 +66,8 @@ enum { VAENMF_ACT_NONE = 0, VAENMF_ACT_TANH = 1, VAENMF_ACT_RELU = 2, VAENMF_ACT
        VAENMF_ACT_STEP = 4 };   /* 1 if x > 0 else 0: sigmoid(x) > 0.5, scripts/evaluate_M2_vad.py:131 */
 
 typedef struct {
-  int32_t F;          /* frequency bins, n_fft/2+1 (<= 640)                         */
+  int32_t F;          /* frequency bins, n_fft/2+1: any value in 1..640 (n_fft need not be a power of two; padding bins
+                         F..Fs-1 of every output are zero)                          */
   int32_t K;          /* NMF rank (<= 32)                                           */
   int32_t L;          /* latent dimension (this build: 32)                          */
   int32_t H1, H2;     /* decoder hidden sizes, first and second layer (this build: 128,128) */

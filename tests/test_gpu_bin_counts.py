@@ -1,0 +1,587 @@
+"""The EM kernels at bin counts other than 16k + 1.
+
+Every power-of-two STFT gives F = n_fft/2 + 1 = 16k + 1 bins, and the kernels are laid out round that: the plan takes the
+odd last bin out of the MFMA tiles (Fm = F - 1), the streaming kernels give a lane four consecutive bins.  Any other F --
+stft() takes any n_fft in [16, 4096], vaenmf_plan_create any F in 1..640 -- leaves a partly filled last bin tile, and
+often a partly filled last 4-bin chunk (Fm % 4 != 0).  One sweep over F runs every EM kernel against the numpy oracle
+from identical inputs; shape_class() restates the dispatch of plan.hip / chain.hip / stream.hip, a CPU test checks that
+the sweep reaches every kernel form the dispatch has, and the GPU tests check that the library reports the kernels
+shape_class() predicts -- a later change of the dispatch makes the sweep fail instead of silently uncovering a kernel.
+
+Tolerances are the ones tests/test_gpu_parity.py states for the same operations (its docstring and the docstrings of
+test_m_step_and_chain_other_shapes, test_bench_mode_m_step_against_the_oracle, test_wave_chain_bf16_mode,
+test_stored_m_step_and_wiener_match_the_decoding_ones, test_fused_w_statistics_equal_the_two_kernel_path).
+"""
+import os
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+import torch
+
+import vaenmf_oracle as orc
+from helpers import GOLDEN, nrm_err, rel_err
+from test_gpu_parity import make_engine, need_gpu
+
+gpu = pytest.mark.gpu        # (per test, not per module: test_sweep_reaches_every_dispatch_class runs without a GPU)
+
+# F -> why it is in the sweep
+SWEEP = {
+    9: "n_fft 16, the smallest; one partial tile; F <= 16 keeps Fm = F; F % 4 = 1",
+    16: "Fs == F, one exact tile",
+    17: "smallest odd-last-bin shape, Fm = 16",
+    64: "4 tiles, exact multiple",
+    80: "5 tiles exact: last F with the W3 lo fragments in LDS in bf16x3 mode",
+    81: "Fm = 80, the chain sees 6 tiles: first L2-streamed lo fragments",
+    201: "n_fft 400 (25 ms): F % 4 = 1, F % 16 = 9",
+    221: "n_fft 440 / 441: F % 16 = 13; 14 chain tiles, even Tm",
+    250: "team geometry 3 with a partial tile; F % 4 = 2",
+    251: "n_fft 500: F % 4 = 3 (three real bins and one padding bin in the last chunk)",
+    256: "n_fft 510: Fs == F, one full chunk",
+    260: "F % 4 = 0, F % 16 = 4: the 17-tile kernels with a partial tile",
+    272: "upper edge of 17 tiles, Fs == F",
+    273: "Fm = 272, 18 chain tiles: first shape on the team chain; NCH = 2",
+    321: "n_fft 640: team geometry 0 at its 20-tile edge",
+    442: "n_fft 882",
+    501: "n_fft 1000: geometry 4 with a partial tile, F % 16 = 5",
+    512: "Fs == F, 32 tiles",
+    514: "the 33-tile bf16 kernels with a nearly empty last tile; NCH = 3",
+    528: "33 tiles full, Fs == F",
+    529: "Fm = 528, 34 tiles: team chain",
+    640: "the maximum; 40 tiles; NCH = 3 ends at lane 31",
+}
+# bf16x3 mode: (F, rank, samples per frame)
+X3_CASES = [(F, 10, 10) for F in SWEEP] + [(201, 8, 30), (260, 8, 30), (514, 8, 30), (250, 32, 10), (640, 32, 10)]
+RUN_F = [9, 201, 250, 273, 501, 514, 640]
+# bf16 (the bench mode)
+BF16_F = [9, 64, 81, 201, 221, 250, 251, 260, 272, 442, 501, 514, 528, 640]
+BF16_CASES = [(F, 8, 30) for F in BF16_F] + [(201, 10, 10), (514, 10, 10)]
+COUNTS = [21, 40, 9]
+N_WAVE_TILES = sum((n + 15) // 16 for n in COUNTS)
+# generator seed of a case's inputs when it is not 1000 + F (a case whose oracle margins leave out more than 15 % of the frames)
+SEEDS = {}
+
+
+def shape_class(F, K, precision, n_wave_tiles, R=30, n_cus=256):
+    """The dispatch of plan.hip (vaenmf_plan_create), chain.hip (vn_wchain_supported, vn_launch_wchain) and stream.hip
+    (launch_stream, launch_st, w_fused_ok, w_group_ok) with every switch at its default.  n_wave_tiles: 16-frame groups
+    of the batch; R: samples per frame of the stored M-step; n_cus: compute units of the device."""
+    bf16 = precision == "bf16"
+    Fs = (F + 15) // 16 * 16
+    Fm = F - 1 if (F % 16 == 1 and F > 16) else F            # plan.hip: the odd last bin leaves the tiles
+    Kp = 8 if K <= 8 else (16 if K <= 16 else 32)
+    team_tiles = (Fm + 15) // 16
+    geom = 3 if team_tiles == 16 else (0 if team_tiles <= 20 else (4 if team_tiles == 32 else 2))
+    tiles = (F + 15) // 16                                   # the wave chain keeps every bin on the MFMA path
+    if tiles > 17 and not (tiles == 33 and bf16):
+        chain_kernel, chain_form = 0, "team"
+    elif bf16 and tiles in (17, 33) and n_wave_tiles <= n_cus:
+        chain_kernel, chain_form = 2, "wchain4<%d>" % tiles
+    else:
+        chain_kernel = 1
+        chain_form = ("wchain<33,GT33>" if tiles == 33 else "wchain<17,exact>" if tiles == 17 else "wchain<5,exact>" if tiles == 5
+                      else "wchain<5>" if tiles < 5 else "wchain<17>")
+    nch = (Fm + 255) // 256
+    w_fused = 0
+    if bf16 and Kp == 8 and nch == 1 and R in (10, 30):
+        w_fused = 2 if n_wave_tiles <= n_cus else 1
+    return dict(Fs=Fs, Fm=Fm, Kp=Kp, chain_tiles=tiles, chain_kernel=chain_kernel, chain_form=chain_form,
+                partial_tile=F % 16 != 0, lo_in_lds=(not bf16) and tiles <= 5, pair_tiles=((tiles - 1) & ~1) if bf16 else 0,
+                team_tiles=team_tiles, geom=geom, nch=nch, tail=Fm % 4 != 0,
+                w_in_lds=Kp <= 8 or Fs * Kp * 4 <= 72 * 1024, w_fused=w_fused)
+
+
+def test_sweep_reaches_every_dispatch_class():
+    """No GPU: the sweep holds at least one F for every kernel form that no 16k + 1 shape reaches, and every F % 4."""
+    x3 = [shape_class(F, K, "bf16x3", N_WAVE_TILES, R) for F, K, R in X3_CASES]
+    bf = [shape_class(F, K, "bf16", N_WAVE_TILES, R) for F, K, R in BF16_CASES]
+    both = x3 + bf
+    Fx3, Fbf = [c[0] for c in X3_CASES], [c[0] for c in BF16_CASES]
+    assert set(Fx3) == set(SWEEP) and set(Fbf) <= set(SWEEP) and set(RUN_F) <= set(SWEEP)
+    for prec, cls in (("bf16x3", x3), ("bf16", bf)):
+        # wave chain with fewer than 5 bin tiles (MAXT = 5, not exact), with and without a partial tile
+        assert any(c["chain_form"] == "wchain<5>" and c["partial_tile"] for c in cls), prec
+        assert any(c["chain_form"] == "wchain<5>" and not c["partial_tile"] for c in cls), prec
+        # 6..16 tiles (MAXT = 17, not exact) with a partial last tile
+        assert any(c["chain_form"] == "wchain<17>" and c["partial_tile"] for c in cls), prec
+        # the 17-tile kernels with a partial last tile and with Fs == F
+        assert any(c["chain_tiles"] == 17 and c["partial_tile"] for c in cls), prec
+        assert any(c["chain_tiles"] == 17 and not c["partial_tile"] for c in cls), prec
+        # three 256-bin chunks in the streaming kernels; a partly filled 4-bin chunk with 1, 2 and 3 chunks
+        assert any(c["nch"] == 3 for c in cls), prec
+        assert {c["nch"] for c in cls if c["tail"]} == {1, 2, 3}, prec
+        # W of a rank above 16 read from global memory because it does not fit LDS (bf16x3 sweep), and one that fits
+        assert prec == "bf16" or any(not c["w_in_lds"] for c in cls)
+    assert any(c["chain_form"] == "wchain<5,exact>" and c["lo_in_lds"] for c in x3)       # F = 80
+    assert any(c["chain_form"] == "wchain<17>" and not c["lo_in_lds"] and c["chain_tiles"] == 6 for c in x3)   # F = 81
+    # the 33-tile bf16 kernels, nearly empty and full last tile; both the four-wavefront and the one-wavefront form exist
+    assert any(c["chain_tiles"] == 33 and c["partial_tile"] for c in bf) and any(c["chain_tiles"] == 33 and not c["partial_tile"] for c in bf)
+    assert {c["chain_kernel"] for c in bf} == {0, 1, 2} and {c["chain_kernel"] for c in x3} == {0, 1}
+    # team kernel geometries 3 / 4 ("no tile checks") with a partial last tile, geometry 2 above 32 tiles, geometry 0 at 20 tiles
+    assert any(c["geom"] == 3 and c["partial_tile"] for c in both) and any(c["geom"] == 4 and c["partial_tile"] for c in both)
+    assert any(c["geom"] == 2 and c["team_tiles"] > 32 for c in both)
+    assert any(c["geom"] == 0 and c["team_tiles"] == 20 for c in both)
+    assert {c["geom"] for c in x3 if c["chain_form"] == "team"} == {0, 2, 4}       # (geometry 3 runs under VAENMF_TEAM_CHAIN=1)
+    # F <= 16 (Fm = F even when F % 16 == 1 could hold) and Fs == F (no padding at all) at 1, 2 and 3 chunks
+    assert any(F <= 16 and F % 16 != 0 for F in SWEEP) and {shape_class(F, 10, "bf16x3", 6)["nch"] for F in SWEEP if F % 16 == 0} == {1, 2, 3}
+    # bf16 tile pairing Tm = (tiles - 1) & ~1: even and odd tile counts with a partial last tile
+    assert any(c["partial_tile"] and c["chain_kernel"] and c["chain_tiles"] % 2 == 0 for c in bf)
+    assert any(c["partial_tile"] and c["chain_kernel"] and c["chain_tiles"] % 2 == 1 for c in bf)
+    # the fused / group W-statistics kernels with a partly filled chunk
+    assert any(c["w_fused"] == 2 and c["tail"] for c in bf)
+    # every residue of F mod 4 beside the 16k + 1 shapes
+    for Fl in (Fx3, Fbf):
+        assert {F % 4 for F in Fl if F % 16 != 1} == {0, 1, 2, 3}
+        assert any(F % 16 == 1 and F > 16 for F in Fl)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+def _inputs(F, K, R, Dy=0):
+    """The recipe of test_m_step_and_chain_other_shapes: ragged batch, tilted spectrogram, Xavier decoder."""
+    params = orc.xavier_normal_params([F, 32, [128, 128]], seed=7, y_dim=Dy, bias_std=0.05)
+    g = np.random.default_rng(SEEDS.get((F, K, R), 1000 + F))
+    NT = sum(COUNTS)
+    c = SimpleNamespace(F=F, K=K, R=R, Dy=Dy, params=params, NT=NT, S_steps=6, ns=3)
+    c.Xs = [((g.standard_normal((n, F)) + 1j * g.standard_normal((n, F))) * (0.5 + 3 * np.exp(-np.arange(F) / 60.0))).astype(np.complex64) for n in COUNTS]
+    c.W0 = [np.maximum(g.random((F, K)), 1e-8).astype(np.float32) for _ in COUNTS]
+    c.H0 = [np.maximum(g.random((K, n)), 1e-8).astype(np.float32) for n in COUNTS]
+    c.ys = [(g.random((n, Dy)) > 0.5).astype(np.float32) for n in COUNTS] if Dy else [None] * len(COUNTS)
+    c.Zs = (0.7 * g.standard_normal((NT, R, 32))).astype(np.float32)
+    c.gains = (0.5 + g.random(NT)).astype(np.float32)
+    c.eps = g.standard_normal((c.S_steps, NT, 32)).astype(np.float32)
+    c.uu = g.random((c.S_steps, NT)).astype(np.float32)
+    c.Z0 = (0.5 * g.standard_normal((NT, 32))).astype(np.float32)
+    c.off = np.concatenate([[0], np.cumsum(COUNTS)])
+    return c
+
+
+def _engine(c, precision, Rcap=None, seeds=None):
+    eng = make_engine(c.params, c.F, c.K, COUNTS, Rcap=Rcap or c.R, precision=precision, seeds=seeds)
+    eng.set_spectrogram(c.Xs)
+    eng.init_nmf(c.W0, c.H0)
+    if c.Dy:
+        eng.set_labels(torch.from_numpy(np.concatenate(c.ys)))
+    eng.g.copy_(torch.from_numpy(c.gains))
+    return eng
+
+
+def _query(eng, what):
+    from vaenmf import _lib
+    return _lib.lib().vaenmf_plan_query(eng._plan, getattr(_lib, what))
+
+
+def _n_cus():
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def _oracle_at(c, eng, u, Zs=None):
+    """The oracle of utterance u in the engine's present state (W, H, g), with the variances of the samples Zs."""
+    sl = eng.utt_slice(u)
+    o = orc.MCEMOracle("M2" if c.Dy else "M1", 1)
+    o.init_parameters(c.Xs[u], c.params, c.K, 1e-8, orc.NumpyRNG(0), y=c.ys[u], W0=eng.W[u, :c.F, :c.K].cpu().numpy(),
+                      H0=eng.Ht[sl, :c.K].cpu().numpy().T.copy())
+    o.g = eng.g[sl].cpu().numpy().copy()
+    if Zs is not None:
+        o.compute_Vs(Zs[sl]); o.compute_Vs_scaled(); o.compute_Vx()
+    return o
+
+
+def _env(**kv):
+    class _E:
+        def __enter__(self):
+            for k, v in kv.items():
+                os.environ[k] = v
+
+        def __exit__(self, *a):
+            for k in kv:
+                os.environ.pop(k, None)
+    return _E()
+
+
+def _padding_is_zero(eng, *tensors):
+    F, K = eng.F, eng.K
+    assert float(eng.W[:, F:].abs().max() if eng.Fs > F else 0) == 0 and float(eng.W[:, :, K:].abs().max() if eng.Kp > K else 0) == 0
+    assert float(eng.Ht[:, K:].abs().max() if eng.Kp > K else 0) == 0
+    for t in tensors:
+        assert float(t[:, F:].abs().max() if eng.Fs > F else 0) == 0
+
+
+def _m_step_against(c, eng, oracles, R, cost, tu, tc, tag):
+    """W, H, g, cost of the engine after its M-step against the oracles' M_step() from the same state and samples."""
+    for name in ("W", "Ht", "g"):
+        assert bool(torch.isfinite(getattr(eng, name)).all()), (tag, name)
+    assert np.all(np.isfinite(cost)), tag
+    for u, o in enumerate(oracles):
+        o.M_step()
+        sl = eng.utt_slice(u)
+        e = (rel_err(eng.W[u, :c.F, :c.K].cpu().numpy(), o.W), rel_err(eng.Ht[sl, :c.K].cpu().numpy().T, o.H),
+             rel_err(eng.g[sl].cpu().numpy(), o.g), abs(cost[u] - o.compute_expected_neg_log_like()) / abs(cost[u]))
+        print("%s F=%d K=%d utt %d: W %.2e H %.2e g %.2e cost %.2e" % ((tag, c.F, c.K, u) + e))
+        assert e[0] < tu and e[1] < tu and e[2] < tu and e[3] < tc, (tag, u, e)
+    _padding_is_zero(eng)
+
+
+def _wiener_against(c, eng, oracles, out, tol, tag, absolute=False):
+    S, Nn, WFs, WFn = out
+    for t in (S, Nn, WFs, WFn):
+        assert bool(torch.isfinite(t).all()), tag
+    F = c.F
+    for u, o in enumerate(oracles):
+        ws, wn = o.compute_WF(sample=False)
+        sl = eng.utt_slice(u)
+        gs, gn = WFs[sl, :F].cpu().numpy().T, WFn[sl, :F].cpu().numpy().T
+        if absolute:      # bf16 mode: masks in [0, 1] to an absolute bound, the filtered spectrograms in L2
+            Sg = np.ascontiguousarray(S[sl, :F].cpu().numpy()).view(np.complex64)[..., 0].T
+            Ng = np.ascontiguousarray(Nn[sl, :F].cpu().numpy()).view(np.complex64)[..., 0].T
+            e = (float(np.max(np.abs(gs - ws))), float(np.max(np.abs(gn - wn))), nrm_err(Sg, ws * o.X), nrm_err(Ng, wn * o.X))
+        else:
+            e = (rel_err(gs, ws), rel_err(gn, wn))
+        print("%s F=%d K=%d utt %d: Wiener " % (tag, F, c.K, u) + " ".join("%.2e" % v for v in e))
+        assert max(e) < tol, (tag, u, e)
+    _padding_is_zero(eng, WFs, WFn, S.abs().sum(-1), Nn.abs().sum(-1))
+
+
+@gpu
+@pytest.mark.parametrize("F", [0, 641])
+def test_bin_counts_out_of_range_are_refused(F):
+    need_gpu()
+    from vaenmf._lib import VaenmfError
+    from vaenmf.engine import BatchEngine
+    dec = [np.zeros((128, 32), np.float32), np.zeros(128, np.float32), np.zeros((128, 128), np.float32), np.zeros(128, np.float32),
+           np.zeros((F, 128), np.float32), np.zeros(F, np.float32)]
+    with pytest.raises(VaenmfError, match=r"F=%d out of range \(1\.\.640\)" % F):
+        BatchEngine(F, 4, dec, max_frames=16, max_utts=1)
+
+
+@gpu
+@pytest.mark.parametrize("F,K,R", X3_CASES)
+def test_split_mode_kernels_against_the_oracle(F, K, R):
+    """bf16x3 mode at one F: decoding kernel, Wiener filter and M-step over given samples, a replayed MH chain with the
+    default kernel and with the team kernel, then the sample store: stored variances, streaming M-step and streaming
+    Wiener filter against the oracle from the chain's own samples."""
+    need_gpu()
+    c = _inputs(F, K, R)
+    sc = shape_class(F, K, "bf16x3", N_WAVE_TILES, R, _n_cus())
+    eng = _engine(c, "bf16x3")
+    assert eng.Fs == sc["Fs"] == _query(eng, "Q_FS") and eng.Kp == sc["Kp"]
+    NT = c.NT
+    eng.Zs.copy_(torch.from_numpy(c.Zs))
+    # 1. decoder
+    Vs = eng.decode(R).cpu().numpy()
+    ref = orc.decoder_forward(c.params, c.Zs.reshape(-1, 32)).reshape(NT, R, F)
+    e = rel_err(Vs[:, :, :F], ref)
+    print("decode F=%d: %.2e" % (F, e))
+    assert e < 2e-4
+    assert np.all(Vs[:, :, F:] == 0)
+    # 2. Wiener filter from the given samples
+    oracles = [_oracle_at(c, eng, u, c.Zs) for u in range(len(COUNTS))]
+    _wiener_against(c, eng, oracles, eng.wiener(R, want_masks=True), 5e-4, "decoding")
+    # 3. M-step and cost
+    eng.m_step(R)
+    _m_step_against(c, eng, oracles, R, eng.cost_from_frames(R), 1e-3, 2e-4, "decoding M-step")
+    # 4. one replayed chain from this state: the oracle's trace first (it alone says which frames are comparable)
+    refs = []
+    for u in range(len(COUNTS)):
+        sl = eng.utt_slice(u)
+        o = _oracle_at(c, eng, u)
+        draws = []
+        for m in range(c.S_steps):
+            draws += [c.eps[m, sl].T.copy(), c.uu[m, sl].copy()]
+        o.rng = orc.ReplayRNG(draws)
+        tr = []
+        Zs_ref = o.sample_posterior(c.Z0[sl].T.copy(), c.ns, c.S_steps - c.ns, trace=tr)
+        ref_acc = np.stack([t["acc"] for t in tr])
+        keep = np.abs(np.log(c.uu[:, sl]) - ref_acc).min(0) > 1e-2       # decisions are only comparable away from the threshold
+        refs.append((sl, ref_acc, Zs_ref, keep))
+    left_out = 1.0 - np.concatenate([r[3] for r in refs]).mean()
+    print("chain F=%d K=%d: frames left out %.1f %%" % (F, K, 100 * left_out))
+    assert left_out <= 0.15
+    dev = eng.device
+    for team in (False, True):
+        with _env(VAENMF_TEAM_CHAIN="1" if team else "0"):
+            eng.Z.copy_(torch.from_numpy(c.Z0))
+            eng.Zs.zero_()
+            acc = eng.mh_chain(c.ns, c.S_steps - c.ns, 0.01, eps=torch.from_numpy(c.eps).to(dev), u=torch.from_numpy(c.uu).to(dev),
+                               want_acc=True).cpu().numpy()
+            assert _query(eng, "Q_CHAIN_KERNEL") == (0 if team else sc["chain_kernel"])
+        for sl, ref_acc, Zs_ref, keep in refs:
+            ea = float(np.max(np.abs(acc[:, sl] - ref_acc)))
+            ez = float(np.max(np.abs(eng.Zs[sl, :c.ns].cpu().numpy()[keep] - Zs_ref[keep]), initial=0.0))
+            ezl = float(np.max(np.abs(eng.Z[sl].cpu().numpy()[keep] - Zs_ref[keep, -1]), initial=0.0))
+            print("chain F=%d K=%d team=%d: acc %.2e Zs %.2e Z %.2e" % (F, K, team, ea, ez, ezl))
+            assert ea < 3e-3 and ez < 1e-5 and ezl < 1e-5, (team, ea, ez, ezl)
+    # 5. the sample store: chains with the device generator, with burn-in and without
+    eng.sample_store(True)
+    for call, (ns, bi) in enumerate(((10, 4), (7, 0))):
+        eng.mh_chain(ns, bi, 0.01, call=call)
+        assert _query(eng, "Q_CHAIN_KERNEL") == sc["chain_kernel"]
+        Zc = eng.Zs[:, :ns].cpu().numpy().copy()
+        got = eng.stored_variances(ns).cpu().numpy()
+        ref = orc.decoder_forward(c.params, Zc.reshape(-1, 32)).reshape(NT, ns, F)
+        e = rel_err(got[:, :, :F], ref)
+        print("store F=%d (%d, %d): %.2e" % (F, ns, bi, e))
+        assert np.all(np.isfinite(got)) and e < 2e-4
+        oracles = [_oracle_at(c, eng, u, Zc) for u in range(len(COUNTS))]
+        eng.m_step_stored()
+        assert _query(eng, "Q_W_FUSED") == sc["w_fused"] == 0
+        _m_step_against(c, eng, oracles, ns, eng.cost_from_frames(ns), 1e-3, 2e-4, "stored M-step (%d, %d)" % (ns, bi))
+        _wiener_against(c, eng, oracles, eng.wiener_stored(want_masks=True), 5e-4, "stored (%d, %d)" % (ns, bi))
+    eng.sample_store(False)
+
+
+@gpu
+@pytest.mark.parametrize("F", RUN_F)
+def test_fused_run_at_other_bin_counts(F):
+    """BatchEngine.run() (the sample store on by default): finite, bit-identical to the same run stepped through mh_chain /
+    m_step_stored / wiener_stored, and the middle utterance alone gives the bits it gives inside the batch."""
+    need_gpu()
+    c = _inputs(F, 10, 12)
+    seeds = [5, 6, 7]
+    niter, nsE, biE, nsW, biW = 3, 6, 5, 12, 7
+
+    def prep(idx):
+        eng = make_engine(c.params, F, c.K, [COUNTS[i] for i in idx], Rcap=12, seeds=[seeds[i] for i in idx])
+        eng.set_spectrogram([c.Xs[i] for i in idx])
+        eng.init_nmf([c.W0[i] for i in idx], [c.H0[i] for i in idx])
+        eng.Z.copy_(torch.from_numpy(np.concatenate([c.Z0[c.off[i]:c.off[i + 1]] for i in idx])))
+        return eng
+
+    eng = prep([0, 1, 2])
+    cost, S, N = eng.run(niter, nsE, biE, nsW, biW, 0.01)
+    assert _query(eng, "Q_MSTEP_PATH") == 1
+    assert bool(torch.isfinite(cost).all()) and bool(torch.isfinite(S).all()) and bool(torch.isfinite(N).all())
+    assert float(S.abs().max()) > 0 and float(S[:, F:].abs().max() if eng.Fs > F else 0) == 0
+    eng2 = prep([0, 1, 2])
+    eng2.sample_store(True)
+    c2 = np.zeros((3, niter))
+    for it in range(niter):
+        eng2.mh_chain(nsE, biE, 0.01, call=it)
+        eng2.m_step_stored()
+        c2[:, it] = eng2.cost_from_frames(nsE)
+    eng2.mh_chain(nsW, biW, 0.01, call=niter, update_Z=False)
+    S2, N2, _, _ = eng2.wiener_stored()
+    assert torch.equal(S, S2) and torch.equal(N, N2)
+    assert np.max(np.abs(c2 - cost.cpu().numpy()) / np.abs(c2)) < 1e-12
+    eng3 = prep([1])
+    cost3, S3, N3 = eng3.run(niter, nsE, biE, nsW, biW, 0.01)
+    sl = eng.utt_slice(1)
+    assert torch.equal(S[sl], S3) and torch.equal(N[sl], N3) and np.array_equal(cost[1].cpu().numpy(), cost3.cpu().numpy()[0])
+
+
+@gpu
+@pytest.mark.parametrize("F,K,R", BF16_CASES)
+def test_bench_mode_kernels_against_the_oracle(F, K, R):
+    """bf16 mode at one F: decoding kernel; a replayed chain with every chain kernel the shape has (first-step
+    log-acceptances against the oracle, wave against team kernel, four-wavefront against one-wavefront form); the
+    stored M-step and Wiener filter against the oracle's from the chain's own samples, with every W-statistics kernel the
+    shape has."""
+    need_gpu()
+    c = _inputs(F, K, R)
+    sc = shape_class(F, K, "bf16", N_WAVE_TILES, R, _n_cus())
+    NT, nu = c.NT, len(COUNTS)
+
+    def fresh():
+        eng = _engine(c, "bf16", seeds=[3, 4, 5])
+        eng.Z.copy_(torch.from_numpy(c.Z0))
+        return eng
+
+    # 7. decoder
+    eng = fresh()
+    assert eng.Fs == sc["Fs"] == _query(eng, "Q_FS") and eng.Kp == sc["Kp"]
+    eng.Zs.copy_(torch.from_numpy(c.Zs))
+    Vs = eng.decode(R).cpu().numpy()
+    e = rel_err(Vs[:, :, :F], orc.decoder_forward(c.params, c.Zs.reshape(-1, 32)).reshape(NT, R, F))
+    print("decode bf16 F=%d: %.2e" % (F, e))
+    assert e < 5e-2 and np.all(Vs[:, :, F:] == 0)
+
+    def chain(**env):
+        with _env(**env):
+            eng = fresh()
+            acc = eng.mh_chain(c.ns, c.S_steps - c.ns, 0.01, eps=torch.from_numpy(c.eps).to(eng.device),
+                               u=torch.from_numpy(c.uu).to(eng.device), want_acc=True).cpu().numpy()
+            return acc, eng.Zs[:, :c.ns].cpu().numpy().copy(), eng.Z.cpu().numpy().copy(), _query(eng, "Q_CHAIN_KERNEL")
+
+    dflt, team = chain(), chain(VAENMF_TEAM_CHAIN="1")
+    assert dflt[3] == sc["chain_kernel"] and team[3] == 0
+    assert np.all(np.isfinite(dflt[0])) and np.all(np.isfinite(team[0]))
+    for u in range(nu):
+        sl = slice(c.off[u], c.off[u + 1])
+        o = orc.MCEMOracle("M1", 1)
+        o.init_parameters(c.Xs[u], c.params, K, 1e-8, orc.NumpyRNG(0), W0=c.W0[u], H0=c.H0[u])
+        o.g = c.gains[sl].copy()
+        draws = []
+        for m in range(c.S_steps):
+            draws += [c.eps[m, sl].T.copy(), c.uu[m, sl].copy()]
+        o.rng = orc.ReplayRNG(draws)
+        tr = []
+        o.sample_posterior(c.Z0[sl].T.copy(), c.ns, c.S_steps - c.ns, trace=tr)
+        # (only the first step is comparable for every frame: afterwards a chain whose decision differs is in another state)
+        for name, out in (("default", dflt), ("team", team)):
+            e = float(np.max(np.abs(out[0][0, sl] - tr[0]["acc"])))
+            print("chain bf16 F=%d K=%d utt %d %s: first-step acc %.3f" % (F, K, u, name, e))
+            assert e < 0.5
+    if sc["chain_kernel"]:
+        e = float(np.max(np.abs(dflt[0] - team[0])))
+        print("chain bf16 F=%d K=%d: wave - team %.3f" % (F, K, e))
+        assert e < 0.1
+
+    # 8. / 9. the store: chain, streaming M-step, streaming Wiener filter
+    def stored(**env):
+        with _env(**env):
+            eng = fresh()
+            eng.sample_store(True)
+            acc = eng.mh_chain(R, 4, 0.01, call=0, want_acc=True)
+            r = SimpleNamespace(eng=eng, chain_kernel=_query(eng, "Q_CHAIN_KERNEL"), acc=acc.cpu().numpy(), Z=eng.Z.cpu().numpy().copy(),
+                                Zs=eng.Zs[:, :R].cpu().numpy().copy(), rows=eng.stored_variances(R).cpu().numpy())
+            r.oracles = [_oracle_at(c, eng, u, r.Zs) for u in range(nu)]
+            r.cf = eng.m_step_stored().cpu().numpy().copy()
+            r.w_fused = _query(eng, "Q_W_FUSED")
+            r.cost = eng.cost_from_frames(R)
+            r.upd = [t.cpu().numpy().copy() for t in (eng.W, eng.Ht, eng.g)] + [r.cf]
+            r.wf = eng.wiener_stored(want_masks=True)
+            return r
+
+    a = stored()
+    assert a.chain_kernel == sc["chain_kernel"] and a.w_fused == sc["w_fused"]
+    assert np.all(np.isfinite(a.rows)) and np.abs(a.Zs - c.Z0[:, None, :]).max() > 0.05
+    _m_step_against(c, a.eng, a.oracles, R, a.cost, 3e-2, 3e-3, "bench M-step")
+    _wiener_against(c, a.eng, a.oracles, a.wf, 1e-2, "bench stored", absolute=True)
+    names = ("W", "Ht", "g", "cost")
+    if sc["w_fused"] == 2:
+        b = stored(VAENMF_WGROUP="0")          # the tile kernel: bit for bit (test_group_w_statistics_equal_the_tile_kernel_bit_for_bit)
+        assert b.w_fused == 1
+        for x, y, name in zip(a.upd, b.upd, names):
+            assert np.array_equal(x, y), name
+        b = stored(VAENMF_WFUSED="0")          # the two-kernel path: the order of the float sums over frames (2e-5)
+        assert b.w_fused == 0
+        for x, y, name in zip(a.upd, b.upd, names):
+            e = float(np.max(np.abs(x - y) / (np.abs(y) + 1e-20)))
+            print("W statistics F=%d fused - two kernels %s: %.2e" % (F, name, e))
+            assert e < 2e-5, name
+    if sc["chain_kernel"] == 2:
+        b = stored(VAENMF_WCHAIN4="0")         # the one-wavefront form: bit for bit
+        assert b.chain_kernel == 1
+        d = chain(VAENMF_WCHAIN4="0")
+        assert d[3] == 1
+        for x, y, name in zip(dflt[:3], d[:3], ("acc", "Zs", "Z")):
+            assert np.array_equal(x, y), "replayed " + name
+        for x, y, name in zip([a.acc, a.Zs, a.Z, a.rows] + a.upd, [b.acc, b.Zs, b.Z, b.rows] + b.upd, ("acc", "Zs", "Z", "rows") + names):
+            assert np.array_equal(x, y), name
+
+
+@gpu
+@pytest.mark.parametrize("variant", ["m2_labels", "nonmf_gains_only"])
+@pytest.mark.parametrize("F", [201, 514])
+def test_stored_path_variants_against_the_oracle(F, variant):
+    """bf16 mode, stored path, the two configurations beside M1 + NMF: M2 (Dy = 1 labels folded into a per-frame layer-1
+    bias) and a fixed noise PSD (gains-only M-step, mcem.py:543-578), against the oracle from the chain's own samples."""
+    need_gpu()
+    K, R = (8, 10) if variant == "m2_labels" else (1, 10)
+    c = _inputs(F, K, R, Dy=1)
+    nu = len(COUNTS)
+    eng = _engine(c, "bf16", seeds=[3, 4, 5])
+    eng.Z.copy_(torch.from_numpy(c.Z0))
+    Vb = None
+    if variant == "nonmf_gains_only":
+        Vb = (np.random.default_rng(F).random((c.NT, F)) + 0.1).astype(np.float32)
+        Vbp = torch.zeros(eng.NT, eng.Fs)
+        Vbp[:, :F] = torch.from_numpy(Vb)
+        eng.set_noise_psd(Vbp.cuda())
+    eng.sample_store(True)
+    eng.mh_chain(R, 4, 0.01, call=0)
+    Zs = eng.Zs[:, :R].cpu().numpy().copy()
+    assert np.abs(Zs - c.Z0[:, None, :]).max() > 0.05
+    if variant == "m2_labels":
+        oracles = [_oracle_at(c, eng, u, Zs) for u in range(nu)]
+        eng.m_step_stored()
+        _m_step_against(c, eng, oracles, R, eng.cost_from_frames(R), 3e-2, 3e-3, "M2 stored M-step")
+        _wiener_against(c, eng, oracles, eng.wiener_stored(want_masks=True), 1e-2, "M2 stored", absolute=True)
+        return
+    oracles = []
+    for u in range(nu):
+        sl = eng.utt_slice(u)
+        o = orc.MCEMOracleNoNMF(c.Xs[u], Vb[sl], c.gains[sl], c.Z0[sl], c.ys[u], c.params, 1, orc.NumpyRNG(0))
+        o.compute_Vs(Zs[sl]); o.compute_Vs_scaled(); o.compute_Vx()
+        o.M_step()
+        oracles.append(o)
+    eng.m_step_stored()
+    cost = eng.cost_from_frames(R)
+    assert bool(torch.isfinite(eng.g).all()) and np.all(np.isfinite(cost))
+    for u, o in enumerate(oracles):
+        sl = eng.utt_slice(u)
+        e = (rel_err(eng.g[sl].cpu().numpy(), o.g), abs(cost[u] - o.compute_expected_neg_log_like()) / abs(cost[u]))
+        print("noNMF F=%d utt %d: g %.2e cost %.2e" % (F, u, e[0], e[1]))
+        assert e[0] < 3e-2 and e[1] < 3e-3
+    out = eng.wiener_stored(want_masks=True)
+    _wiener_against(c, eng, oracles, out, 1e-2, "noNMF stored", absolute=True)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+class _Recorder:
+    def __init__(self, seed):
+        self.g, self.draws = orc.NumpyRNG(seed), []
+
+    def rand(self, *shape):
+        self.draws.append(self.g.rand(*shape))
+        return self.draws[-1]
+
+    def randn(self, *shape):
+        self.draws.append(self.g.randn(*shape))
+        return self.draws[-1]
+
+
+@gpu
+def test_reconstructor_at_25_ms():
+    """wav -> stft (n_fft 400, F = 201) -> fused EM run in bench mode -> istft on three synthetic utterances."""
+    need_gpu()
+    from vaenmf.pipeline import Reconstructor
+    from vaenmf.synth import synth_utterance
+    lens = [16000, 23457, 12001]
+    xs = [synth_utterance(10 + i, n_samples=T)[2] for i, T in enumerate(lens)]
+    params = orc.xavier_normal_params([201, 32, [128, 128]], seed=0)
+    rec = Reconstructor(params, 201, 10, niter=3, fs=16000, wlen_sec=25e-3, precision="bf16", max_frames=1024, max_utts=4)
+    wav = torch.from_numpy(np.concatenate(xs).astype(np.float32)).cuda()
+    s_hat, n_hat, cost = rec.enhance(wav, lens)
+    assert _query(rec.eng, "Q_MSTEP_PATH") == 1
+    assert s_hat.shape[0] == sum(lens) and n_hat.shape[0] == sum(lens) and cost.shape == (3, 3)
+    assert torch.isfinite(s_hat).all() and torch.isfinite(n_hat).all() and torch.isfinite(cost).all()
+    o = 0
+    for T in lens:
+        assert float(s_hat[o:o + T].abs().max()) > 0
+        o += T
+
+
+@gpu
+def test_mcem_at_25_ms():
+    """stft (F = 201) -> MCEM_M1 in bf16x3 mode with replayed draws, against the oracle run on the oracle's STFT with the
+    same draws: the bounds of test_mcem_at_the_reference_default_window."""
+    need_gpu()
+    import vaenmf
+    from vaenmf import stft as vstft
+    x = (np.load(GOLDEN + "/metrics_dummy_m2.npz")["a_s"] / 32768.0)[:24000]
+    F, K, niter = 201, 10, 3
+    params = orc.xavier_normal_params([F, 32, [128, 128]], seed=3)
+    Xo = orc.stft(x, fs=16000, wlen_sec=25e-3).T                       # (N, F)
+    rec = _Recorder(7)
+    o = orc.MCEMOracle("M1", niter, 10, 10, 10, 10, 0.01)
+    o.init_parameters(Xo, params, K, 1e-8, rec)                         # records the draws it takes
+    c_ref = o.run()
+    vae = vaenmf.VariationalAutoencoder([F, 32, [128, 128]])
+    vae.load_state_dict({k: torch.tensor(v) for k, v in params.items()})
+    m = vaenmf.MCEM_M1(niter, 10, 10, 10, 10, 0.01, rng="replay", precision="bf16x3")
+    X = vstft.stft(x, fs=16000, wlen_sec=25e-3)
+    assert X.shape == (F, Xo.shape[0])
+    it = iter(rec.draws)
+    _r, _n = torch.rand, torch.randn
+    torch.rand = lambda *s, **k: torch.tensor(next(it))
+    torch.randn = lambda *s, **k: torch.tensor(next(it))
+    try:
+        m.init_parameters(X=X.T, vae=vae, nmf_rank=K, eps=1e-8, device="cuda:0")
+        c = m.run()
+    finally:
+        torch.rand, torch.randn = _r, _n
+    ec, es = float(np.max(np.abs(c - c_ref) / np.abs(c_ref))), nrm_err(m.S_hat, o.S_hat)
+    print("MCEM_M1 F=201: cost %.2e S_hat %.2e" % (ec, es))
+    assert ec < 2e-4 and es < 2e-3
+    s = vstft.istft(m.S_hat, fs=16000, wlen_sec=25e-3, max_len=len(x))
+    assert len(s) == len(x) and np.all(np.isfinite(s)) and np.abs(s).max() > 0

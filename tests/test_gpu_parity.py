@@ -436,6 +436,7 @@ def test_m_step_and_chain_other_shapes(F, K, R, model):
     eng.Z.copy_(torch.from_numpy(Z0))
     acc = eng.mh_chain(ns, S_steps - ns, 0.01, eps=torch.from_numpy(eps).to(eng.device), u=torch.from_numpy(uu).to(eng.device),
                        want_acc=True).cpu().numpy()
+    n_kept = 0
     for u, o in enumerate(oracles):
         sl = eng.utt_slice(u)
         o.W = eng.W[u, :F, :K].cpu().numpy(); o.H = eng.Ht[sl, :K].cpu().numpy().T.copy(); o.g = eng.g[sl].cpu().numpy()
@@ -447,10 +448,13 @@ def test_m_step_and_chain_other_shapes(F, K, R, model):
         tr = []
         Zs_ref = o.sample_posterior(Z0[sl].T.copy(), ns, S_steps - ns, trace=tr)
         ref_acc = np.stack([t["acc"] for t in tr])
-        margin = np.abs(np.log(uu[:, sl]) - ref_acc)
         assert np.max(np.abs(acc[:, sl] - ref_acc)) < 3e-3
-        if margin.min() > 1e-2:                     # decisions are only comparable away from the threshold
-            assert np.max(np.abs(eng.Zs[sl, :ns].cpu().numpy() - Zs_ref)) < 1e-5
+        # decisions are only comparable away from the threshold: a frame's samples are compared when every one of its
+        # decision margins (from the oracle alone) exceeds 1e-2, and at most 15 % of the batch's frames may be left out
+        keep = np.abs(np.log(uu[:, sl]) - ref_acc).min(0) > 1e-2
+        n_kept += int(keep.sum())
+        assert np.max(np.abs(eng.Zs[sl, :ns].cpu().numpy()[keep] - Zs_ref[keep]), initial=0.0) < 1e-5
+    assert NT - n_kept <= 0.15 * NT, "%d of %d frames are too close to a decision threshold to compare" % (NT - n_kept, NT)
 
 
 @pytest.mark.parametrize("F,model", [(257, "M1"), (513, "M1"), (257, "M2"), (65, "M1")])
