@@ -421,11 +421,12 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1) ? ST_WAVES : 2) void wst
   using RBt = RowBatch<NCH, ST>;
   int n_beg, n_end;
   wave_frames(a.NT, n_beg, n_end);
-  if (a.R <= RBt::RB) {
-    // The frame fits one batch: two half batches, each refilled with the NEXT frame's rows as soon as it has been
+  using Half = RowBatch<NCH, ST, 2>;
+  constexpr int HB = Half::RB;
+  // (2 * HB, not RB: float rows in three chunks have RB = 5 and HB = 2, and the second half dropped row 4 of a 5-row frame)
+  if (a.R <= 2 * HB) {
+    // The frame fits two half batches, each refilled with the NEXT frame's rows as soon as it has been
     // consumed, so that half a frame of loads is in flight while the other half is computed.
-    using Half = RowBatch<NCH, ST, 2>;
-    constexpr int HB = Half::RB;
     Half h0, h1;
     auto base_of = [&](int n) { return reinterpret_cast<const ST*>(a.VsS) + (size_t)n * a.Rs * a.Fs; };
     const int R0 = a.R < HB ? a.R : HB;              // rows of the first half

@@ -8,6 +8,9 @@ Stated tolerances (float32 unless noted):
   * W, H, g after an M-step from identical samples: 5e-4 relative; cost: 1e-4 relative.
   * trajectories with replayed noise: decisions identical on the golden cases (they were
     chosen with decision margins >= 1e-3), final S_hat 2e-3 relative (L2).
+  * from the device's own variances (tests/test_gpu_rank_and_samples.py: the oracle's formulas in float64, fed with
+    eng.stored_variances / eng.decode, both precision modes): W, H, g, the masks (absolute) and S_hat / N_hat (L2) within
+    max(2e-5, 16 e32), the cost within max(1e-6, 16 e32), e32 being the float32 oracle's own error against float64.
 """
 import os
 
