@@ -1,16 +1,20 @@
 // M-step and Wiener filter over the sample-variance store (EM.M_step mcem.py:90-152, cost :68-70,
-// compute_WF :486-488): the variances Vs[n][r][f] of the chain's samples were written to HBM by
-// mh_chain_kernel (engine.hip, STORE), so these kernels stream them instead of running the decoder
-// again.  They are plain bandwidth kernels: one wavefront owns one frame at a time, a lane owns four
-// consecutive bins per 256-bin chunk (one 1 KiB row segment per load instruction), the samples are a
-// sequential loop, and everything a frame needs beyond its own row -- sums over bins for H, g and the
+// compute_WF :486-488): the variances Vs[n][r][f] of the chain's samples are written to HBM, with the slot map src, by the
+// chain kernels in their STORE instantiations -- wchain_kernel / wchain4_kernel (chain.hip), mh_chain_kernel (engine.hip) --
+// so these kernels stream them instead of running the decoder again.  They are plain bandwidth kernels: one wavefront owns
+// one frame at a time, a lane owns four consecutive bins per 256-bin chunk (one 1 KiB row segment per load instruction),
+// the samples are a sequential loop, and everything a frame needs beyond its own row -- sums over bins for H, g and the
 // cost -- is a wavefront reduction (DPP / permlane, no LDS, no barrier).
 //
-//   wstats_stream   A1 = sum_r 1/Vx, P = X2 sum_r 1/Vx^2 with the pre-update W, H, g        (:107-109)
+//   wstats_stream   A1 = sum_r 1/Vx, P = X2 sum_r 1/Vx^2 with the pre-update W, H, g (:107-109), any shape
+//   wstats_stream2  the same, frame-pipelined: one chunk, rank <= 8, the frame fits one batch of rows
+//   wstats_fused    the same and the W update's sums over frames (:108-109) in one pass, per 64-frame tile (the bench shapes)
+//   wstats_group    the sums of wstats_fused for small batches, one workgroup per 16-frame group
 //   hg_stream       H <- H sqrt(num/den) with the updated W (:118-121), refreshed Vb (:124-125),
 //                   g <- g sqrt(num/den) (:138-142), cost with the refreshed variances (:70, :151-152);
 //                   three passes over the frame's rows, which stay in registers when they fit one batch
 //   wf_stream       Wiener masks mean_r(g Vs/Vx), mean_r(Vb/Vx) and S_hat, N_hat            (:486-488, :175-176)
+// stream_form() at the end of the file decides which of them runs and with which compile-time parameters.
 //
 // Bins of the odd last bin and the padding (f >= Fm: F-1 when F = 16k+1) are handled as one extra
 // element that every lane computes redundantly (same address: a broadcast load).
@@ -59,6 +63,9 @@ struct StreamArgs {
 __device__ __forceinline__ float wave_sum(float v) { return sum_rows4(sum_row16(v)); }
 // a value every lane holds alike, kept in a scalar register from here on
 __device__ __forceinline__ float vn_uniform(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); }
+// lane l's value of v as a wave-uniform scalar (l: compile time or uniform).  v by reference: by value, the copy the
+// bit cast then reads changes the instruction order of the kernels that use it.
+__device__ __forceinline__ float read_lane(const float& v, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)); }
 
 template <int NCH, int KP, typename ST, bool TAIL = false>
 struct FrameCtx {
@@ -111,12 +118,8 @@ struct FrameCtx {
         for (int t = 1; t < 4; ++t) v[c][t] = ok(c, t) ? v[c][t] : pad;
     }
   }
-  __device__ __forceinline__ float nwk(int k) const {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, nw), k));
-  }
-  __device__ __forceinline__ float wxk(int k) const {       // W[utt][F-1][k], wave-uniform (k: compile time)
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, wx), k));
-  }
+  __device__ __forceinline__ float nwk(int k) const { return read_lane(nw, k); }
+  __device__ __forceinline__ float wxk(int k) const { return read_lane(wx, k); }       // W[utt][F-1][k], wave-uniform (k: compile time)
   // workgroup prologue (rank > 8): stage W of the utterance of the workgroup's first frame
   __device__ __forceinline__ void stage_block_w() {
     if (WPRIV || !a.w_blk_lds) return;
@@ -164,7 +167,6 @@ struct FrameCtx {
 #pragma unroll
     for (int j = 0; j < 4; ++j) wl[(k + j) * a.Fs + f] = v[j];
   }
-  template <bool L>
   __device__ __forceinline__ const float* w_row(int utt, int f) const {   // global layout only
     return a.W + ((size_t)utt * a.Fs + f) * KP;
   }
@@ -198,7 +200,7 @@ struct FrameCtx {
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           float v = 0.f;
-          const float* wrow = w_row<L>(utt, f0[c] + t);
+          const float* wrow = w_row(utt, f0[c] + t);
 #pragma unroll
           for (int k = 0; k < KP; k += 4) {
             // (one fused multiply-add per rank, in rank order: the order and rounding of the LDS form above, so that a frame's
@@ -239,7 +241,7 @@ struct FrameCtx {
         } else {
 #pragma unroll
           for (int t = 0; t < 4; ++t) {
-            const float w = w_row<L>(utt, f0[c] + t)[k];
+            const float w = w_row(utt, f0[c] + t)[k];
             nu += w * P[c][t];
             de += w * A[c][t];
           }
@@ -284,7 +286,17 @@ struct FrameCtx {
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 rcp2(const f32x2 x) { return f32x2{fast_rcp(x[0]), fast_rcp(x[1])}; }
 __device__ __forceinline__ f32x2 log2_2(const f32x2 x) { return f32x2{fast_log2(x[0]), fast_log2(x[1])}; }
+// One sample's term of the W statistics for a lane's four bins: q = 1/(g Vs + Vb), A1 += q, A2 += q^2.  Two bins per
+// instruction (v_pk_fma / v_pk_add_f32: next to transcendentals a packed instruction costs the issue slot of a plain
+// one -- tools/ubench/overlap.hip)
+__device__ __forceinline__ void wstat_term(const f32x4 v, const f32x4 vb, const f32x2 g2, f32x4& a1, f32x4& a2) {
+  const f32x2 q0 = rcp2(g2 * v.lo + vb.lo), q1 = rcp2(g2 * v.hi + vb.hi);
+  a1.lo += q0; a1.hi += q1;
+  a2.lo = q0 * q0 + a2.lo; a2.hi = q1 * q1 + a2.hi;
+}
 
+// rows per batch of `elt`-byte elements in nch chunks (div = 2: half batches); stream_form() asks as well
+constexpr int row_batch_rows(int elt, int nch, int div) { return (elt == 2 ? 32 : 16) / nch / div; }
 // A batch of up to RB rows of one frame in registers (this lane's bins, still packed as stored): every load of
 // the batch is issued before the first use, so a wavefront keeps RB x 0.5-1 KiB in flight -- the kernels are
 // latency-bound otherwise (86 % of the wave time in s_waitcnt with 4 loads in flight) -- and the H / g / cost
@@ -295,7 +307,7 @@ template <int NCH, typename ST, int DIV = 1, int RT = 0, int RBX = 0>
 struct RowBatch {
   // rows per batch; RBX > 0 overrides (hg_stream with two 256-bin chunks of bf16 rows: 32 rows x 4 registers hold a whole
   // 30-sample frame, so its three passes read the rows once instead of re-reading two batches of 16 in every pass)
-  static constexpr int RB = RBX > 0 ? RBX : (sizeof(ST) == 2 ? 32 : 16) / NCH / DIV;
+  static constexpr int RB = RBX > 0 ? RBX : row_batch_rows((int)sizeof(ST), NCH, DIV);
   static_assert(RT <= RB, "RT");
   __device__ __forceinline__ bool on(int r) const { return RT > 0 ? r < RT : r < nr; }
   using raw_t = typename std::conditional<sizeof(ST) == 4, f32x4, bf16x4>::type;
@@ -592,13 +604,7 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1 && sizeof(ST) == 2) ? ST_
           f32x4 v[NCH];
           rb.get(r, v);
 #pragma unroll
-          for (int c = 0; c < NCH; ++c) {
-            // two bins per instruction (v_pk_fma / v_pk_add_f32: next to transcendentals a packed instruction costs the
-            // issue slot of a plain one -- tools/ubench/overlap.hip)
-            const f32x2 q0 = rcp2(gn2 * v[c].lo + vb[c].lo), q1 = rcp2(gn2 * v[c].hi + vb[c].hi);
-            a1[c].lo += q0; a1[c].hi += q1;
-            a2[c].lo = q0 * q0 + a2[c].lo; a2[c].hi = q1 * q1 + a2[c].hi;
-          }
+          for (int c = 0; c < NCH; ++c) wstat_term(v[c], vb[c], gn2, a1[c], a2[c]);
         };
         rb.for_rows(row1);
         const float q = fast_rcp(gn * rb.x() + vbx) * rb.xmask(fc);
@@ -806,7 +812,6 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1) ? ST_WAVES : 2) void wf_
   }
 }
 
-
 // ---------------------------------------------------------------------------------------------------------------
 // Frame-pipelined forms (the frame's samples fit one register batch: R <= RowBatch::RB).  Two wavefronts per SIMD
 // with 256 registers each instead of four with 128: a wavefront holds TWO batches, the frame it computes on and the
@@ -824,7 +829,7 @@ struct FrameSmall {            // the per-frame operands besides the rows, reque
   int utt;
   __device__ __forceinline__ void get_h(float (&h)[KP]) const {
 #pragma unroll
-    for (int k = 0; k < KP; ++k) h[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, hl), k));
+    for (int k = 0; k < KP; ++k) h[k] = read_lane(hl, k);
   }
 };
 
@@ -865,12 +870,7 @@ __global__ __launch_bounds__(256, 2) void wstats_stream2_kernel(const StreamArgs
         f32x4 v[NCH];
         rb.get(r, v);
 #pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-          const f32x2 g2 = {s.g, s.g};
-          const f32x2 q0 = rcp2(g2 * v[c].lo + vb[c].lo), q1 = rcp2(g2 * v[c].hi + vb[c].hi);
-          a1[c].lo += q0; a1[c].hi += q1;
-          a2[c].lo = q0 * q0 + a2[c].lo; a2[c].hi = q1 * q1 + a2[c].hi;
-        }
+        for (int c = 0; c < NCH; ++c) wstat_term(v[c], vb[c], f32x2{s.g, s.g}, a1[c], a2[c]);
       }
     }
     const float q = fast_rcp(s.g * rb.x() + vbx) * rb.xmask(fc);
@@ -900,9 +900,9 @@ __global__ __launch_bounds__(256, 2) void wstats_stream2_kernel(const StreamArgs
   }
 }
 
-
 // ============================================================================
-// Rotating registers (bf16 rows, one 256-bin chunk, rank <= 8, exactly RT samples per frame): the bench shapes.
+// Rotating registers (bf16 rows, one 256-bin chunk, rank <= 8, exactly RT samples per frame), the frame loop of
+// wstats_fused_kernel.
 // A wavefront keeps ONE frame's rows in registers (2 per row) and refills each row's registers with the same row of
 // the NEXT frame right after its last use, so RT row loads stay in flight per wavefront all the time and the loop is
 // straight-line: the compiler's vmcnt counts are exact (wait for the oldest row only), which no form with per-row
@@ -917,7 +917,7 @@ struct RotSmall {              // a frame's operands besides the rows
   // lane KP+2: X2 of the extra bin.  Read back with readlane at the first use, two frames later -- a scalar taken at the
   // load (the compiler moves a uniform value to an SGPR at once) would wait there, for every older row load as well.
   float pk;
-  __device__ __forceinline__ float lane_f(int l) const { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, pk), l)); }
+  __device__ __forceinline__ float lane_f(int l) const { return read_lane(pk, l); }
   __device__ __forceinline__ int utt() const { return __builtin_amdgcn_readlane(__builtin_bit_cast(int, pk), KP); }
   __device__ __forceinline__ float g() const { return lane_f(KP + 1); }
   __device__ __forceinline__ float x2x() const { return lane_f(KP + 2); }
@@ -985,10 +985,12 @@ struct RotCtx {
   __device__ __forceinline__ float xmask() const { return (fc.has_x && fc.lane < RT) ? 1.f : 0.f; }
 };
 
+// (FrameSmall::get_h is the same loop over a member.  One function for both, its argument by value or by reference, changes
+// the instruction order of wstats_stream2_kernel or of wstats_fused_kernel: two spellings stay.)
 template <int KP>
 __device__ __forceinline__ void rot_h(float hl, float (&h)[KP]) {
 #pragma unroll
-  for (int k = 0; k < KP; ++k) h[k] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, hl), k));
+  for (int k = 0; k < KP; ++k) h[k] = read_lane(hl, k);
 }
 
 // ----------------------------------------------------------------------------
@@ -1065,10 +1067,7 @@ __global__ __launch_bounds__(256, 2) void wstats_fused_kernel(const StreamArgs a
         const unsigned vnext = more ? rc.voff : 0xF0000000u;
 #pragma unroll
         for (int r = 0; r < RT; ++r) {
-          const f32x4 v = rc.template row<S>(r);
-          const f32x2 q0 = rcp2(g2 * v.lo + vb[0].lo), q1 = rcp2(g2 * v.hi + vb[0].hi);
-          a1.lo += q0; a1.hi += q1;
-          a2.lo = q0 * q0 + a2.lo; a2.hi = q1 * q1 + a2.hi;
+          wstat_term(rc.template row<S>(r), vb[0], g2, a1, a2);
           rc.template req_row<T>(nn, sl[T], r, a2[3], vnext);
           __builtin_amdgcn_sched_barrier(0);             // one row per region
         }
@@ -1128,7 +1127,6 @@ __global__ __launch_bounds__(256, 2) void wstats_fused_kernel(const StreamArgs a
     }
   }
 }
-
 
 // ----------------------------------------------------------------------------
 // The same sums for SMALL batches (no more 16-frame groups than CUs: one utterance through the drop-in classes).  In
@@ -1200,9 +1198,7 @@ __global__ __launch_bounds__(256, 2) void wstats_group_kernel(const StreamArgs a
         auto row1 = [&](int r) {
           f32x4 v[1];
           rb.get(r, v);
-          const f32x2 q0 = rcp2(g2 * v[0].lo + vb[0].lo), q1 = rcp2(g2 * v[0].hi + vb[0].hi);
-          a1.lo += q0; a1.hi += q1;
-          a2.lo = q0 * q0 + a2.lo; a2.hi = q1 * q1 + a2.hi;
+          wstat_term(v[0], vb[0], g2, a1, a2);
         };
         rb.for_rows(row1);
         const float q = fast_rcp(gn * rb.x() + vbx) * rb.xmask(fc);
@@ -1262,7 +1258,6 @@ __global__ __launch_bounds__(256, 2) void wstats_group_kernel(const StreamArgs a
   }
 }
 
-
 StreamArgs base_args(const vaenmf_plan* p) {
   StreamArgs a = {};
   a.VsS = p->VsS; a.src = p->src; a.frame_utt = p->d_frame_utt; a.Vb = p->Vb_ext;
@@ -1273,78 +1268,126 @@ StreamArgs base_args(const vaenmf_plan* p) {
 }
 
 enum { SK_WSTATS, SK_HG, SK_WF };
+enum { W_TWO_KERNELS = 0, W_FUSED = 1, W_GROUP = 2 };     // the W-statistics path, as VAENMF_Q_W_FUSED reports it
 
-template <int KIND, int NCH, int KP, typename ST>
-int launch_st(StreamArgs a, int grid, hipStream_t st, bool tail) {
-  // rank <= 8: one W[utt] per wavefront; above: one per workgroup when it leaves room for two workgroups per CU
-  const size_t one = (size_t)a.Fs * KP * sizeof(float);
-  const size_t lds = KP <= 8 ? 4 * one : (one <= 72 * 1024 ? one : 0);
-  a.w_blk_lds = KP > 8 && lds > 0;
-  auto go = [&](auto* fn, int g) -> int {
-    if (int e = vn_ensure_dyn_lds((const void*)fn, 80 * 1024)) return e;
-    hipLaunchKernelGGL(fn, dim3(g), dim3(256), lds, st, a);
-    return 0;
-  };
-  if constexpr (KIND == SK_WSTATS) {
-    if constexpr (NCH == 1 && KP <= 8) {
-      if (a.R <= RowBatch<NCH, ST>::RB) {
-        // frame-pipelined form: two resident wavefronts per SIMD, one resident set per launch.  (The same form of the H/g
-        // kernel was measured twice, 0.23 ms against 0.17-0.20 for the batch-at-a-time one at four wavefronts per SIMD,
-        // and is not kept; exact-row-count instantiations of this one spill: 0.29 vs 0.155 ms.)
-        int g2 = a.n_sms * 2;
-        if (g2 * 4 > a.NT) g2 = (a.NT + 3) / 4;
-        return go(wstats_stream2_kernel<NCH, KP, ST, 0>, g2);
-      }
-    }
-    return go(wstats_stream_kernel<NCH, KP, ST>, grid);
-  } else if constexpr (KIND == SK_HG) {
-    if (tail) return go(hg_stream_kernel<NCH, KP, ST, 0, true>, grid);      // Fm % 4 != 0: per-bin validity (FrameCtx)
-    if constexpr (NCH == 1 && KP <= 8) {
-      // exact-sample-count instantiations (one chunk, rank <= 8): no per-row branches, rows consumed as they arrive (precise
-      // vmcnt counts): 0.198 -> 0.172 ms.  (Slower while the extra-bin addresses still spilled.)  (The rotating-register form
-      // needs two register sets of 60 plus the three passes' working set: it spills at 256 registers with 30 samples --
-      // 0.62 ms against 0.17 for the batch form -- and gains nothing with 10; not kept.)
-      if (a.R == 30) return go(hg_stream_kernel<NCH, KP, ST, 30>, grid);
-      if (a.R == 10) return go(hg_stream_kernel<NCH, KP, ST, 10>, grid);
-    } else if constexpr (NCH == 2 && sizeof(ST) == 2 && KP == 16) {
-      // two 256-bin chunks (F = 513), rank 16, bf16 rows: the whole 30-sample frame sits in one batch of registers
-      // (RBX = 32): the exact-count form drops the per-row branches here as well (F = 513, K = 10: 0.2625 -> 0.250 ms)
-      if (a.R == 30) return go(hg_stream_kernel<NCH, KP, ST, 30>, grid);
-    }
-    return go(hg_stream_kernel<NCH, KP, ST>, grid);
-  } else {
-    if (tail) return go(wf_stream_kernel<NCH, KP, ST, true>, grid);
-    return go(wf_stream_kernel<NCH, KP, ST>, grid);
-  }
-}
-template <int KIND, int NCH, int KP>
-int launch_one(const StreamArgs& a, int grid, hipStream_t st) {
-  const bool tail = (a.Fm & 3) != 0;                    // the chunk that holds bin Fm-1 is partly padding
-  if (a.store_f32) return launch_st<KIND, NCH, KP, float>(a, grid, st, tail);
-  return launch_st<KIND, NCH, KP, __bf16>(a, grid, st, tail);
-}
-template <int KIND, int NCH>
-int launch_kp(const StreamArgs& a, int Kp, int grid, hipStream_t st) {
-  switch (Kp) {
-    case 8: return launch_one<KIND, NCH, 8>(a, grid, st);
-    case 16: return launch_one<KIND, NCH, 16>(a, grid, st);
-    default: return launch_one<KIND, NCH, 32>(a, grid, st);
-  }
-}
-template <int KIND>
-int launch_stream(const vaenmf_plan* p, const StreamArgs& a, hipStream_t st) {
+// The form of a streaming launch: every compile-time parameter of the kernels and the choice between them, decided in
+// stream_form() and nowhere else.
+struct StreamForm {
+  int nch, kp;               // 256-bin chunks per row (1..3), padded rank (8, 16, 32)
+  bool f32;                  // rows are float (bf16x3 mode) rather than bf16
+  bool tail;                 // Fm % 4 != 0: the chunk that holds bin Fm-1 is partly padding, per-bin validity (FrameCtx)
+  int hg_rt;                 // H/g: the exact-sample-count instantiation (30 or 10); 0: any count
+  bool pipelined;            // W statistics, two-kernel path: wstats_stream2_kernel
+  int w_path;                // W_TWO_KERNELS, W_FUSED or W_GROUP
+};
+
+StreamForm stream_form(const vaenmf_plan* p, const StreamArgs& a) {
+  StreamForm f = {};
   const int nch = (p->Fm + 255) / 256;
+  f.nch = nch <= 1 ? 1 : (nch == 2 ? 2 : 3);
+  f.kp = (p->Kp == 8 || p->Kp == 16) ? p->Kp : 32;
+  f.f32 = a.store_f32 != 0;
+  f.tail = (a.Fm & 3) != 0;
+  const bool small = f.nch == 1 && f.kp == 8;           // one chunk, rank <= 8
+  // H/g, exact-sample-count instantiations: no per-row branches, rows consumed as they arrive (precise vmcnt counts).
+  //   one chunk, rank <= 8: 0.198 -> 0.172 ms.  (Slower while the extra-bin addresses still spilled.)  (The rotating-register
+  //     form needs two register sets of 60 plus the three passes' working set: it spills at 256 registers with 30 samples --
+  //     0.62 ms against 0.17 for the batch form -- and gains nothing with 10; not kept.)
+  //   two 256-bin chunks (F = 513), rank 16, bf16 rows: the whole 30-sample frame sits in one batch of registers (RBX = 32),
+  //     so the exact-count form drops the per-row branches here as well (F = 513, K = 10: 0.2625 -> 0.250 ms)
+  if (!f.tail && ((small && (a.R == 30 || a.R == 10)) || (f.nch == 2 && !f.f32 && f.kp == 16 && a.R == 30))) f.hg_rt = a.R;
+  // W statistics, frame-pipelined form (the frame fits one batch): two resident wavefronts per SIMD, one resident set per
+  // launch.  (The same form of the H/g kernel was measured twice, 0.23 ms against 0.17-0.20 for the batch-at-a-time one at
+  // four wavefronts per SIMD, and is not kept; exact-row-count instantiations of this one spill: 0.29 vs 0.155 ms.)
+  f.pipelined = small && a.R <= row_batch_rows(f.f32 ? 4 : 2, 1, 1);
+  // W statistics + the W update's sums in one kernel: the bench shapes (bf16 rows, one 256-bin chunk, rank <= 8, 30 or 10
+  // samples per frame, NMF noise model); VAENMF_WFUSED=0 keeps the two-kernel path (A/B runs, tests).  Small batches (no
+  // more 16-frame groups than CUs): one workgroup per group; VAENMF_WGROUP=0 keeps the tile kernel (tests).
+  f.w_path = W_TWO_KERNELS;
+  if (!f.f32 && p->Kp == 8 && nch == 1 && (a.R == 30 || a.R == 10) && !a.gains_only && vn_switches().wfused)
+    f.w_path = (p->wpart16 && p->n_wtiles <= p->n_sms && vn_switches().wgroup) ? W_GROUP : W_FUSED;
+  return f;
+}
+
+template <int V> using ic = std::integral_constant<int, V>;
+template <typename T> struct type_of { using type = T; };
+// The one switch over the compile-time parameters: fn(ic<NCH>, ic<KP>, type_of<ST>) with the form's chunks, padded rank
+// and row type; what fn instantiates of them (if constexpr) is the set of kernels in the object.
+template <typename FN>
+int with_form(const StreamForm& f, FN fn) {
+  auto rows = [&](auto nch, auto kp) { return f.f32 ? fn(nch, kp, type_of<float>{}) : fn(nch, kp, type_of<__bf16>{}); };
+  auto rank = [&](auto nch) { return f.kp == 8 ? rows(nch, ic<8>{}) : (f.kp == 16 ? rows(nch, ic<16>{}) : rows(nch, ic<32>{})); };
+  return f.nch == 1 ? rank(ic<1>{}) : (f.nch == 2 ? rank(ic<2>{}) : rank(ic<3>{}));
+}
+
+template <int KIND>
+int launch_stream(const vaenmf_plan* p, StreamArgs a, const StreamForm& f, hipStream_t st) {
   // enough wavefronts in flight to cover the HBM latency: 4 per SIMD, blocks of 4 wavefronts
   // exactly one resident set of wavefronts (4 per SIMD at rank 8): the W-statistics kernel pipelines its loads
   // across the frames of a wavefront and wants long runs (blocks per CU 4: 0.169 ms, 6: 0.220, 8: 0.179, 12: 0.192);
   // H/g is indifferent (4: 0.287, 8: 0.291, 16: 0.305)
   int grid = p->n_sms * 4;
   if (grid * 4 > p->NT) grid = (p->NT + 3) / 4;
-  int rc;
-  if (nch <= 1) rc = launch_kp<KIND, 1>(a, p->Kp, grid, st);
-  else if (nch == 2) rc = launch_kp<KIND, 2>(a, p->Kp, grid, st);
-  else rc = launch_kp<KIND, 3>(a, p->Kp, grid, st);
+  const int rc = with_form(f, [&](auto nch, auto kp, auto row) -> int {
+    constexpr int NCH = decltype(nch)::value, KP = decltype(kp)::value;
+    using ST = typename decltype(row)::type;
+    // rank <= 8: one W[utt] per wavefront; above: one per workgroup when it leaves room for two workgroups per CU
+    const size_t one = (size_t)a.Fs * KP * sizeof(float);
+    const size_t lds = KP <= 8 ? 4 * one : (one <= 72 * 1024 ? one : 0);
+    a.w_blk_lds = KP > 8 && lds > 0;
+    auto go = [&](auto* fn, int g) -> int {
+      if (int e = vn_ensure_dyn_lds((const void*)fn, 80 * 1024)) return e;
+      hipLaunchKernelGGL(fn, dim3(g), dim3(256), lds, st, a);
+      return 0;
+    };
+    if constexpr (KIND == SK_WSTATS) {
+      if constexpr (NCH == 1 && KP <= 8) {
+        if (f.pipelined) {
+          int g2 = a.n_sms * 2;
+          if (g2 * 4 > a.NT) g2 = (a.NT + 3) / 4;
+          return go(wstats_stream2_kernel<NCH, KP, ST, 0>, g2);
+        }
+      }
+      return go(wstats_stream_kernel<NCH, KP, ST>, grid);
+    } else if constexpr (KIND == SK_HG) {
+      if (f.tail) return go(hg_stream_kernel<NCH, KP, ST, 0, true>, grid);
+      if constexpr (NCH == 1 && KP <= 8) {
+        if (f.hg_rt == 30) return go(hg_stream_kernel<NCH, KP, ST, 30>, grid);
+        if (f.hg_rt == 10) return go(hg_stream_kernel<NCH, KP, ST, 10>, grid);
+      } else if constexpr (NCH == 2 && sizeof(ST) == 2 && KP == 16) {
+        if (f.hg_rt == 30) return go(hg_stream_kernel<NCH, KP, ST, 30>, grid);
+      }
+      return go(hg_stream_kernel<NCH, KP, ST>, grid);
+    } else {
+      if (f.tail) return go(wf_stream_kernel<NCH, KP, ST, true>, grid);
+      return go(wf_stream_kernel<NCH, KP, ST>, grid);
+    }
+  });
   if (rc) return rc;
+  VN_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
+// the fused and the group W-statistics kernels (rank 8, bf16 rows, exactly 30 or 10 samples per frame)
+int launch_w_tiles(const vaenmf_plan* p, StreamArgs a, const StreamForm& f, hipStream_t st) {
+  const bool group = f.w_path == W_GROUP;
+  const size_t lds = ((size_t)a.Fs * 8 + (size_t)(group ? 1 : 4) * wf_acc_floats<8>()) * sizeof(float);
+  a.t64_n0 = p->d_t64_n0; a.t64_cnt = p->d_t64_cnt; a.n_t64 = p->n_t64; a.wpart64 = p->wpart64;
+  int grid = a.n_sms * 2;                               // tiles: one resident set, 2 workgroups of 4 wavefronts per CU
+  const int g = vn_switches().wfused_grid;              // (tests: a small grid makes every workgroup walk several tiles / utterances)
+  if (g > 0 && g < grid) grid = g;
+  if (grid > p->n_t64) grid = p->n_t64;
+  auto go = [&](auto rt) -> int {
+    constexpr int RT = decltype(rt)::value;
+    if (group) {
+      hipLaunchKernelGGL((wstats_group_kernel<8, RT, __bf16>), dim3(p->n_wtiles), dim3(256), lds, st, a, p->d_wt_n0, p->d_wt_cnt, p->n_wtiles, p->wpart16);
+      return 0;
+    }
+    if (int e = vn_ensure_dyn_lds((const void*)wstats_fused_kernel<8, RT>, 80 * 1024)) return e;
+    hipLaunchKernelGGL((wstats_fused_kernel<8, RT>), dim3(grid), dim3(256), lds, st, a);
+    return 0;
+  };
+  if (int e = a.R == 30 ? go(ic<30>{}) : go(ic<10>{})) return e;
   VN_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -1357,43 +1400,6 @@ int check_store(const vaenmf_plan* p) {
 
 }  // namespace
 
-namespace {
-// W statistics + the W update's sums in one kernel: the bench shapes (bf16 rows, one 256-bin chunk, rank <= 8,
-// 30 or 10 samples per frame, NMF noise model).  VAENMF_WFUSED=0 keeps the two-kernel path (A/B runs, tests).
-bool w_fused_ok(const vaenmf_plan* p, const StreamArgs& a) {
-  return !a.store_f32 && p->Kp == 8 && (p->Fm + 255) / 256 == 1 && (a.R == 30 || a.R == 10) && !a.gains_only && vn_switches().wfused;
-}
-// small batches: one workgroup per 16-frame group (VAENMF_WGROUP=0 keeps the tile kernel: tests)
-bool w_group_ok(const vaenmf_plan* p) {
-  return p->wpart16 && p->n_wtiles <= p->n_sms && vn_switches().wgroup;
-}
-int launch_w_group(const vaenmf_plan* p, StreamArgs a, hipStream_t st) {
-  const size_t lds = ((size_t)a.Fs * 8 + (size_t)wf_acc_floats<8>()) * sizeof(float);
-  const int grid = p->n_wtiles;
-  if (a.R == 30) hipLaunchKernelGGL((wstats_group_kernel<8, 30, __bf16>), dim3(grid), dim3(256), lds, st, a, p->d_wt_n0, p->d_wt_cnt, p->n_wtiles, p->wpart16);
-  else hipLaunchKernelGGL((wstats_group_kernel<8, 10, __bf16>), dim3(grid), dim3(256), lds, st, a, p->d_wt_n0, p->d_wt_cnt, p->n_wtiles, p->wpart16);
-  VN_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-int launch_w_fused(const vaenmf_plan* p, StreamArgs a, hipStream_t st) {
-  a.t64_n0 = p->d_t64_n0; a.t64_cnt = p->d_t64_cnt; a.n_t64 = p->n_t64; a.wpart64 = p->wpart64;
-  const size_t lds = ((size_t)a.Fs * 8 + (size_t)4 * wf_acc_floats<8>()) * sizeof(float);
-  int grid = a.n_sms * 2;                               // one resident set: 2 workgroups of 4 wavefronts per CU
-  const int g = vn_switches().wfused_grid;              // (tests: a small grid makes every workgroup walk several tiles / utterances)
-  if (g > 0 && g < grid) grid = g;
-  if (grid > p->n_t64) grid = p->n_t64;
-  if (a.R == 30) {
-    if (int e = vn_ensure_dyn_lds((const void*)wstats_fused_kernel<8, 30>, 80 * 1024)) return e;
-    hipLaunchKernelGGL((wstats_fused_kernel<8, 30>), dim3(grid), dim3(256), lds, st, a);
-  } else {
-    if (int e = vn_ensure_dyn_lds((const void*)wstats_fused_kernel<8, 10>, 80 * 1024)) return e;
-    hipLaunchKernelGGL((wstats_fused_kernel<8, 10>), dim3(grid), dim3(256), lds, st, a);
-  }
-  VN_CHECK_HIP(hipGetLastError());
-  return 0;
-}
-}  // namespace
-
 extern "C" int vaenmf_m_step_stored(vaenmf_plan* p, const float* X2, float* W, float* Ht, float* g, double* cost_frames,
                                     void* stream) {
   if (int e = check_store(p)) return e;
@@ -1401,24 +1407,17 @@ extern "C" int vaenmf_m_step_stored(vaenmf_plan* p, const float* X2, float* W, f
   StreamArgs a = base_args(p);
   a.X2 = X2; a.W = W; a.Ht = Ht; a.g = g; a.A1 = p->A1; a.P = p->P; a.normW = p->normW;
   a.cost_frames = cost_frames ? cost_frames : p->cost_frames;
-  if (p->Vb_ext) {                                      // noNMF: only the gains move (mcem.py:543-578)
-    a.gains_only = 1;
+  a.gains_only = p->Vb_ext != nullptr;                  // noNMF: only the gains move (mcem.py:543-578)
+  const StreamForm f = stream_form(p, a);
+  if (a.gains_only) {
     ProfScope ps(p, VN_K_HG, st);
-    return launch_stream<SK_HG>(p, a, st);
+    return launch_stream<SK_HG>(p, a, f, st);
   }
-  p->last_w_fused = w_fused_ok(p, a) ? 1 : 0;
-  if (p->last_w_fused && w_group_ok(p)) {
-    p->last_w_fused = 2;
-    { ProfScope ps(p, VN_K_WSTATS, st); if (int e = launch_w_group(p, a, st)) return e; }
-    { ProfScope ps(p, VN_K_WUPDATE, st); if (int e = vn_launch_w_update_tiles(p, W, st, true)) return e; }
-  } else if (p->last_w_fused) {
-    { ProfScope ps(p, VN_K_WSTATS, st); if (int e = launch_w_fused(p, a, st)) return e; }
-    { ProfScope ps(p, VN_K_WUPDATE, st); if (int e = vn_launch_w_update_tiles(p, W, st, false)) return e; }
-  } else {
-    { ProfScope ps(p, VN_K_WSTATS, st); if (int e = launch_stream<SK_WSTATS>(p, a, st)) return e; }
-    { ProfScope ps(p, VN_K_WUPDATE, st); if (int e = vn_launch_w_update(p, W, Ht, st)) return e; }
-  }
-  { ProfScope ps(p, VN_K_HG, st); if (int e = launch_stream<SK_HG>(p, a, st)) return e; }
+  p->last_w_fused = f.w_path;
+  const bool two = f.w_path == W_TWO_KERNELS;
+  { ProfScope ps(p, VN_K_WSTATS, st); if (int e = two ? launch_stream<SK_WSTATS>(p, a, f, st) : launch_w_tiles(p, a, f, st)) return e; }
+  { ProfScope ps(p, VN_K_WUPDATE, st); if (int e = two ? vn_launch_w_update(p, W, Ht, st) : vn_launch_w_update_tiles(p, W, st, f.w_path == W_GROUP)) return e; }
+  { ProfScope ps(p, VN_K_HG, st); if (int e = launch_stream<SK_HG>(p, a, f, st)) return e; }
   return 0;
 }
 
@@ -1430,5 +1429,5 @@ extern "C" int vaenmf_wiener_stored(vaenmf_plan* p, const float* W, const float*
   a.W = W; a.Ht = const_cast<float*>(Ht); a.g = const_cast<float*>(g); a.X = X;
   a.S_hat = S_hat; a.N_hat = N_hat; a.WFs = WFs; a.WFn = WFn;
   ProfScope ps(p, VN_K_WF, (hipStream_t)stream);
-  return launch_stream<SK_WF>(p, a, (hipStream_t)stream);
+  return launch_stream<SK_WF>(p, a, stream_form(p, a), (hipStream_t)stream);
 }
