@@ -8,17 +8,18 @@
 // is reproduced operation for operation (the test suite's CPU checker holds the same statement and is
 // pinned against the reference's own outputs, tests/golden/labels_f257.npz):
 //   power     fma(re, re, round(im*im))                      (complex64 product, target.py:16/:37)
-//   total     numpy's pairwise float32 sum                   (np.sum, :19/:40)
+//   total     np.sum's float32 order: the run goes to the add loop in blocks of 8192 elements (numpy's ufunc
+//             buffer), each block is summed pairwise, the block sums are added left to right   (:19/:40)
 //   cumsum    running float32 sum                            (np.cumsum)
 //   per-frame power (VAD): pairwise sum over the F bins of the frame (power.sum(axis=0) on the
-//             Fortran-ordered STFT the reference's stft returns, :38)
+//             Fortran-ordered STFT the reference's stft returns, :38; F <= 640 is a single block)
 // The sort itself is order-free: rocPRIM segmented radix sort (one segment per utterance).
 #include "common.h"
 #include <hipcub/hipcub.hpp>
 
 namespace {
 
-// numpy pairwise_sum over a[0..n) (float32), restated; called by single threads
+// numpy pairwise_sum over a[0..n) (float32), restated (one call of numpy's add loop); called by single threads
 __device__ float pw_block(const float* a, int n) {        // n <= 128
   if (n < 8) {
     float r = 0.f;
@@ -58,6 +59,16 @@ __device__ float pw_sum(const float* a, int64_t n) {
   return ret;
 }
 
+// np.sum over a[0..n): one pw_sum per NP_SUM_BLOCK elements, the block sums added in order.  A single pairwise tree over
+// a longer run rounds differently (the total of an IBM segment of more than 31 frames at F = 257 already does).
+constexpr int64_t NP_SUM_BLOCK = 8192;
+__device__ float np_sum(const float* a, int64_t n) {
+  float r = pw_sum(a, n < NP_SUM_BLOCK ? n : NP_SUM_BLOCK);
+  for (int64_t i = NP_SUM_BLOCK; i < n; i += NP_SUM_BLOCK)
+    r = __fadd_rn(r, pw_sum(a + i, n - i < NP_SUM_BLOCK ? n - i : NP_SUM_BLOCK));
+  return r;
+}
+
 // compact powers [NT][F] (no padding bins)
 __global__ void power_compact_kernel(const float2* __restrict__ X, int NT, int F, int Fs, float* __restrict__ P) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -79,7 +90,7 @@ __global__ void lorenz_threshold_kernel(const float* __restrict__ sorted, const 
   const int u = blockIdx.x;
   const float* s = sorted + seg_off[u];
   const int64_t n = seg_off[u + 1] - seg_off[u];
-  const float total = pw_sum(s, n);
+  const float total = np_sum(s, n);
   float run = 0.f, t = 0.f;
   bool any = false;
   for (int64_t i = 0; i < n; ++i) {

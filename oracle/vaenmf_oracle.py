@@ -520,11 +520,22 @@ def synth_utterance(seed, n_samples=64000, fs=16000):
 # ----------------------------------------------------------------------------
 # Label / guide front-ends (python/processing/target.py)
 # ----------------------------------------------------------------------------
+def heavy_tailed_stft(F, N, seed):
+    """Seeded complex64 (F, N) test spectrogram, Fortran-ordered like the reference's stft output: complex Gaussian bins
+    times a log-normal frame gain exp(1.5 N(0,1)) -- a heavy-tailed power distribution, so the float32 total depends on
+    its summation order.  Input of tests/golden/labels_blocks.npz (only seeds, shapes and outputs are stored)."""
+    g = np.random.default_rng(seed)
+    X = ((g.standard_normal((F, N)) + 1j * g.standard_normal((F, N))) * np.exp(1.5 * g.standard_normal((1, N)))).astype(np.complex64)
+    return np.asfortranarray(X)
+
+
 def pairwise_sum_f32(a):
-    """NumPy's float32 add-reduce over a 1-D run, restated (numpy/_core/src/umath/loops_utils.h.src,
-    pairwise_sum; numpy 2.2 is this image's pinned version): < 8 elements a running sum; <= 128 eight
+    """NumPy's float32 add loop over ONE call's run, restated (numpy/_core/src/umath/loops_utils.h.src,
+    pairwise_sum; numpy 2.2 is the pinned version): < 8 elements a running sum; <= 128 eight
     interleaved partial sums combined as ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) plus the tail; else split at
-    n/2 rounded down to a multiple of 8.  Pins the order the HIP label kernels must reproduce bit for bit."""
+    n/2 rounded down to a multiple of 8.  np.sum calls the loop once per 8192-element block (np_sum_f32 below), so
+    this alone is np.sum only up to 8192 elements -- enough for the per-frame sums over F <= 640 bins.
+    Pins the order the HIP label kernels must reproduce bit for bit."""
     a = np.asarray(a, dtype=np.float32)
     n = len(a)
     f = np.float32
@@ -550,6 +561,24 @@ def pairwise_sum_f32(a):
     return f(pairwise_sum_f32(a[:n2]) + pairwise_sum_f32(a[n2:]))
 
 
+NP_SUM_BLOCK = 8192      # numpy's ufunc buffer size in elements (np.getbufsize())
+
+
+def np_sum_f32(a):
+    """np.sum over a 1-D float32 run, restated: the reduction hands the add loop at most NP_SUM_BLOCK elements at a time
+    (the ufunc buffer size; blocks start at element 0), each block is reduced by pairwise_sum_f32 and the block sums are
+    added to the accumulator left to right.  Up to 8192 elements this is pairwise_sum_f32 itself; beyond, one pairwise
+    tree over the whole run is NOT what numpy computes.  The reversed view `np.sort(...)[::-1]` of target.py:18/:40 sums
+    like its contiguous copy (pinned in tests/test_oracle_golden.py)."""
+    a = np.asarray(a, dtype=np.float32)
+    if len(a) == 0:
+        return np.float32(0.0)
+    r = pairwise_sum_f32(a[:NP_SUM_BLOCK])
+    for i in range(NP_SUM_BLOCK, len(a), NP_SUM_BLOCK):
+        r = np.float32(r + pairwise_sum_f32(a[i:i + NP_SUM_BLOCK]))
+    return r
+
+
 def power_c64(obs):
     """abs(obs * obs.conj()) of a complex64 array as this image's numpy evaluates it (target.py:16, :37):
     the product's real part is fma(re, re, round(im*im)), its imaginary part exactly 0."""
@@ -560,9 +589,10 @@ def power_c64(obs):
 
 def lorenz_threshold(power, quantile_fraction):
     """target.py:18-22 / :39-42: descending sort, Lorenz curve cumsum/sum in float32 (running cumsum,
-    pairwise total), threshold = last sorted value whose Lorenz value is below the fraction."""
+    np.sum's total: pairwise per 8192-element block, blocks added in order), threshold = last sorted value whose
+    Lorenz value is below the fraction."""
     srt = np.sort(np.asarray(power, np.float32), axis=None)[::-1]
-    total = pairwise_sum_f32(srt)
+    total = np_sum_f32(srt)
     run = np.float32(0.0)
     thr = None
     q = np.float32(quantile_fraction)
@@ -590,7 +620,7 @@ def clean_speech_IBM(observations, quantile_fraction=0.98, quantile_weight=0.999
 
 def frame_power(observations):
     """target.py:38: power.sum(axis=0) -- for the (F, N) Fortran-ordered STFT the reference's stft returns,
-    each frame is a contiguous run of F values reduced pairwise."""
+    each frame is a contiguous run of F values reduced pairwise (F <= 640: one block of np.sum)."""
     power = power_c64(observations)
     return np.array([pairwise_sum_f32(power[:, n]) for n in range(power.shape[1])], dtype=np.float32)
 

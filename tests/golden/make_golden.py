@@ -323,6 +323,38 @@ def labels_case():
     np.savez_compressed(os.path.join(HERE, "labels_f257.npz"), **out)
 
 
+def labels_blocks_case():
+    """target.py:7-50 on seeded inputs whose sorted run is longer than numpy's 8192-element reduction buffer: there
+    np.sum(sorted_power) is a sum of per-block pairwise sums, and a label flips when the total is rounded in any other
+    order.  Four IBM inputs (F, N, seed) at q = 0.98 and 0.999 and one VAD input of 8300 frames.  Only the seeds, the
+    shapes and the outputs are stored (labels as uint8; `thr`: sorted_power[lorenz < q][-1] by the same numpy calls);
+    the tests rebuild the inputs with orc.heavy_tailed_stft."""
+    from python.processing import target as ref_target
+
+    def threshold(power, q):                                  # the numpy calls of target.py:18-21 / :40-43
+        srt = np.sort(power, axis=None)[::-1]
+        return srt[np.cumsum(srt) / np.sum(srt) < q][-1]
+
+    ibm = [(65, 130, 2), (65, 130, 11), (257, 33, 23), (33, 257, 21)]
+    vad = [(2, 8300, 4)]
+    qs = [0.98, 0.999]
+    out = {"ibm_cases": np.array(ibm, np.int64), "vad_cases": np.array(vad, np.int64), "q": np.array(qs, np.float64)}
+    for mode, cases, fn in (("ibm", ibm, ref_target.clean_speech_IBM), ("vad", vad, ref_target.clean_speech_VAD)):
+        for c, (F, N, seed) in enumerate(cases):
+            X = orc.heavy_tailed_stft(F, N, seed)
+            power = abs(X * X.conj())
+            if mode == "vad":
+                power = power.sum(axis=0)
+            assert power.size > 8192 and power.dtype == np.float32
+            for j, q in enumerate(qs):
+                y = fn(X, quantile_fraction=q, quantile_weight=0.999)
+                assert y.dtype == np.float32 and set(np.unique(y)) <= {0.0, 1.0}
+                out["%s%d_q%d" % (mode, c, j)] = y.astype(np.uint8)
+                out["%s%d_q%d_thr" % (mode, c, j)] = np.float32(threshold(power, q))
+                print("labels_blocks", mode, (F, N, seed), q, "on", y.mean(), "thr", out["%s%d_q%d_thr" % (mode, c, j)])
+    np.savez_compressed(os.path.join(HERE, "labels_blocks.npz"), **out)
+
+
 def spp_case():
     """python/models/spp_estimation.py:163-235 on the noisy power spectrogram of a seeded synthetic mixture
     (float32 |X|^2 as scripts/evaluate_M2_ibm.py:137-138 builds it).  Only outputs are stored; the input
@@ -396,6 +428,7 @@ if __name__ == "__main__":
     quirk_case()
     mlp_case()
     labels_case()
+    labels_blocks_case()
     spp_case()
     metrics_case()
     # real decoder dims (L=32, H=[128,128]) so the HIP path can run the same cases

@@ -11,6 +11,7 @@ Stated tolerances (float32 unless noted):
   * from the device's own variances (tests/test_gpu_rank_and_samples.py: the oracle's formulas in float64, fed with
     eng.stored_variances / eng.decode, both precision modes): W, H, g, the masks (absolute) and S_hat / N_hat (L2) within
     max(2e-5, 16 e32), the cost within max(1e-6, 16 e32), e32 being the float32 oracle's own error against float64.
+  * label / SPP / mask / dense / Gram front-ends over shapes and edges: the rules in the docstring of tests/test_gpu_front_ends.py.
 """
 import os
 

@@ -149,7 +149,105 @@ def test_label_front_ends_against_reference():
     g = np.random.default_rng(0)
     for n in (1, 7, 8, 9, 127, 128, 129, 257, 1000, 24415):
         a = (g.random(n) ** 4 * 1000).astype(np.float32)
-        assert orc.pairwise_sum_f32(a) == np.sum(a), n
+        assert orc.pairwise_sum_f32(a) == np.sum(a), n      # (24415: only because this light-tailed run rounds alike in either order)
+        assert orc.np_sum_f32(a) == np.sum(a), n
+
+
+NP_SUM_SIZES = list(range(1, 301)) + [1000, 8191, 8192, 8193, 8450, 12864, 16384, 16385, 20000, 24415, 33153]
+
+
+def test_np_sum_restatement_against_numpy():
+    """orc.np_sum_f32 against this image's np.sum on heavy-tailed float32 runs sorted descending -- what
+    np.sum(sorted_power) of target.py:19/:40 reduces -- as a contiguous array and as the [::-1] view the reference
+    sums.  Light-tailed data (the pin above) cannot tell one summation order from another beyond 8192 elements; with
+    exp(3 N(0,1)) a single pairwise tree over the whole run differs from np.sum in about a third of the long runs."""
+    one_tree_differs = 0
+    for n in NP_SUM_SIZES:
+        for seed in range(3 if n <= 300 else 6):
+            g = np.random.default_rng(1000 * seed + n)
+            asc = np.sort(np.exp(3.0 * g.standard_normal(n)).astype(np.float32))
+            view = asc[::-1]                                   # negative stride, as np.sort(power, axis=None)[::-1]
+            dense = np.ascontiguousarray(view)
+            want = np.sum(dense)
+            assert want.dtype == np.float32
+            assert np.sum(view) == want, (n, seed)
+            assert orc.np_sum_f32(dense) == want, (n, seed)
+            assert orc.np_sum_f32(view) == want, (n, seed)
+            if n <= orc.NP_SUM_BLOCK:
+                assert orc.pairwise_sum_f32(dense) == want, (n, seed)
+            else:
+                one_tree_differs += orc.pairwise_sum_f32(dense) != want
+    assert one_tree_differs >= 10, one_tree_differs           # the data can tell the two orders apart
+
+
+LORENZ_BINS = (1, 2, 3, 7, 8, 9, 16, 17, 33, 63, 64, 65, 127, 128, 129, 257, 513, 640)
+LORENZ_FRAMES = (1, 2, 3, 7, 8, 9, 17, 64, 130)
+LORENZ_Q = (0.5, 0.93, 0.98, 0.999)
+
+
+def _numpy_threshold(power, q):
+    """The plain numpy evaluation: sort, cumsum, sum, compare, last entry."""
+    srt = np.sort(power, axis=None)[::-1]
+    with np.errstate(invalid="ignore"):
+        return srt[np.cumsum(srt) / np.sum(srt) < q][-1]
+
+
+def _oracle_threshold(power, q):
+    with np.errstate(invalid="ignore"):
+        return orc.lorenz_threshold(power, q)
+
+
+def test_lorenz_threshold_against_plain_numpy():
+    """orc.lorenz_threshold against numpy's own sort / cumsum / sum / compare over 18 bin counts x 9 frame counts x 4
+    fractions, for the IBM run (all F N powers) and the VAD run (N frame powers): 1296 comparisons, an IndexError where
+    numpy raises one.  Segment sizes go from 1 to 83200, across the 8192-element blocks of np.sum."""
+    n_raise = 0
+    for F in LORENZ_BINS:
+        for N in LORENZ_FRAMES:
+            X = orc.heavy_tailed_stft(F, N, 7 * F + N)
+            for power in (orc.power_c64(X), orc.frame_power(X)):
+                for q in LORENZ_Q:
+                    try:
+                        want = _numpy_threshold(power, q)
+                    except IndexError:
+                        n_raise += 1
+                        with pytest.raises(IndexError, match="index -1 is out of bounds"):
+                            _oracle_threshold(power, q)
+                        continue
+                    assert _oracle_threshold(power, q) == want, (F, N, q, power.shape)
+    assert 0 < n_raise < 300, n_raise
+
+
+def test_lorenz_degenerate_inputs_against_plain_numpy():
+    """All-zero (0/0: no Lorenz value is below the fraction), all-equal and half-zero powers: same threshold or same
+    IndexError as numpy."""
+    for n in (1, 2, 9, 130, 9000):
+        for power in (np.zeros(n, np.float32), np.full(n, 0.3, np.float32), np.r_[np.zeros(n - n // 2), np.full(n // 2, 2.5)].astype(np.float32)):
+            for q in LORENZ_Q:
+                try:
+                    want = _numpy_threshold(power, q)
+                except IndexError:
+                    with pytest.raises(IndexError, match="index -1 is out of bounds"):
+                        _oracle_threshold(power, q)
+                    continue
+                assert _oracle_threshold(power, q) == want, (n, q)
+
+
+def test_block_crossing_labels_against_reference():
+    """tests/golden/labels_blocks.npz: the reference's labels for inputs whose sorted run crosses np.sum's 8192-element
+    blocks (make_golden.py labels_blocks_case).  The oracle reproduces every stored array and threshold exactly."""
+    z = np.load(os.path.join(GOLDEN, "labels_blocks.npz"))
+    for mode, fn in (("ibm", orc.clean_speech_IBM), ("vad", orc.clean_speech_VAD)):
+        for c, (F, N, seed) in enumerate(z[mode + "_cases"]):
+            X = orc.heavy_tailed_stft(int(F), int(N), int(seed))
+            power = orc.power_c64(X) if mode == "ibm" else orc.frame_power(X)
+            assert power.size > orc.NP_SUM_BLOCK
+            for j, q in enumerate(z["q"]):
+                y = fn(X, float(q), 0.999)
+                ref = z["%s%d_q%d" % (mode, c, j)]
+                assert y.dtype == np.float32 and y.shape == ref.shape
+                assert np.array_equal(y, ref), (mode, c, q, int((y != ref).sum()))
+                assert orc.lorenz_threshold(power, float(q)) == z["%s%d_q%d_thr" % (mode, c, j)]
 
 
 def test_spp_estimator_against_reference():
