@@ -71,7 +71,9 @@ struct vaenmf_plan {
   float *b1, *b2, *b3;       // biases (b3 padded to 16*NT3)
   float* w1y;                // [H1][Dy] label columns of W1 (M2)
   int Dy;
-  int Lz;                    // latent dimension of the model (16 or 32): latents Lz..31 of the MFMA path are zero padding
+  int Lz;                    // latent dimension of the model: latents Lz..Lp-1 of the MFMA path are zero padding
+  bool wide = false;         // L > 32 or H1 = 256: the chain is wide.hip's kernel, M-step and Wiener filter stream the store
+  int Lp = LAT;              // latent columns of Z / Zs / the replay draws: 32, or 128 on a wide plan (VAENMF_Q_LP)
   bool one_hidden;           // decoder with ONE hidden layer (h_dim = [128]): layer 2 is skipped
   bool have_weights;
   const float* Vb_ext;       // caller-owned noise variance [NT][Fs] (noNMF variants) or null
@@ -126,7 +128,8 @@ struct vaenmf_plan {
   int seed_pos = 0;
 };
 
-// one MH-chain call, as vaenmf_mh_chain hands it to the kernel launchers (engine.hip team kernel, chain.hip wave kernel)
+// one MH-chain call, as vaenmf_mh_chain hands it to the kernel launchers (engine.hip team kernel, chain.hip wave kernel,
+// wide.hip wide kernel)
 struct VnChainCall {
   const float *X2, *W, *Ht, *g, *B1;
   float *Z, *Zs, *acc_out;
@@ -158,6 +161,8 @@ bool vn_wchain_supported(const vaenmf_plan* p);            // chain.hip
 bool vn_wchain_fits(const vaenmf_plan* p, const VnChainCall& cc);                 // chain.hip
 int vn_launch_wchain(vaenmf_plan* p, const VnChainCall& cc, hipStream_t st);      // chain.hip: builds WcArgs, picks the kernel
 int vn_launch_tchain(vaenmf_plan* p, const VnChainCall& cc, hipStream_t st);      // engine.hip: builds ChainArgs, picks the geometry
+int vn_launch_widechain(vaenmf_plan* p, const VnChainCall& cc, hipStream_t st);   // wide.hip: the chain of a wide plan
+int vn_launch_wide_rng_fill(vaenmf_plan* p, uint32_t call, int S, float* eps_out, float* u_out, hipStream_t st);   // wide.hip
 int vn_launch_w_update(const vaenmf_plan* p, float* W, const float* Ht, hipStream_t st);                // aux.hip
 int vn_launch_w_update_tiles(const vaenmf_plan* p, float* W, hipStream_t st, bool groups);             // aux.hip
 int vn_launch_cost_reduce(const vaenmf_plan* p, const double* cost_frames, size_t stride, int n_it, int R, double* cost, int niter,

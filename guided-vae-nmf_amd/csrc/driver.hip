@@ -30,6 +30,12 @@ extern "C" int vaenmf_mh_chain(vaenmf_plan* p, const float* X2, const float* W, 
                "vaenmf_sample_store(plan, max_samples) after vaenmf_bind_batch (no allocation happens in vaenmf_mh_chain)", p->NT, nsamples);
     cc.VsS = p->VsS; cc.VsS_bytes = need_v; cc.src = p->src; cc.Rs = Rs;
   }
+  if (p->wide) {                                        // wide decoder shapes: one kernel for every batch (wide.hip, 64-bit addresses)
+    ProfScope ps(p, VN_K_CHAIN, st);
+    if (int e = vn_launch_widechain(p, cc, st)) return e;
+    if (p->store_on) { p->store_R = nsamples; p->store_Rs = nsamples + 1; }
+    return 0;
+  }
   // wave-private chains (chain.hip) while every buffer of the batch is within their 32-bit byte offsets; a larger batch
   // (about 300 k frames at 105 samples) runs engine.hip's team kernel, which addresses with 64 bits
   if (vn_wchain_supported(p) && vn_wchain_fits(p, cc)) {
@@ -180,8 +186,9 @@ static int em_run_body(vaenmf_plan* p, const EmCall& c, bool stored, void* strea
   // With the sample-variance store on, the M-step never looks at the E-step's latent samples: the wave-private chain kernels
   // then do not record them (Zs = NULL: 123 MB of writes per launch at the bench shape that nothing reads); the Wiener chain
   // below records its own, which is what Zs holds after the reference's run() too (mcem.py:173, :477-482).
-  float* Zs_e = (stored && !vn_switches().keep_zs && vn_wchain_supported(p) &&
-                 vaenmf_wchain_addressable(p->NT, c.Rcap, c.nsE + c.biE, p->Fs, p->Kp, p->n_utt, 0)) ? nullptr : c.Zs;
+  float* Zs_e = (stored && !vn_switches().keep_zs &&
+                 (p->wide || (vn_wchain_supported(p) &&
+                              vaenmf_wchain_addressable(p->NT, c.Rcap, c.nsE + c.biE, p->Fs, p->Kp, p->n_utt, 0)))) ? nullptr : c.Zs;
   for (int it = 0; it < c.niter; ++it) {                // EM.run, mcem.py:159-165
     rng.call = (uint32_t)it;
     double* cf = p->cost_frames + (size_t)(it % VN_COST_CHUNK) * cstride;
@@ -239,6 +246,10 @@ extern "C" int vaenmf_em_run(vaenmf_plan* p, const float* X2, float* W, float* H
   const size_t esz = p->cfg.precision == VAENMF_PREC_BF16X3 ? sizeof(float) : sizeof(__bf16);
   auto fits = [&](int ns) { return (size_t)(p->NT + 1) * (ns + 1) * p->Fs * esz < 0xE0000000ull; };
   const bool want = p->store_on, stored = want && fits(nsE) && fits(nsWF);
+  // a wide plan has no decoding M-step / Wiener kernels to fall back to
+  VN_REQUIRE(!p->wide || want, "vaenmf_em_run on a wide decoder plan streams the sample store: switch it on with vaenmf_sample_store first");
+  VN_REQUIRE(!p->wide || stored, "vaenmf_em_run on a wide decoder plan: the sample store of %d frames passes the 32-bit offsets of the "
+             "streaming kernels and there is no decoding path for wide decoders; bind a smaller batch", p->NT);
   p->store_on = stored;
   p->last_m_step_path = stored ? 1 : 2;               // VAENMF_Q_MSTEP_PATH: the caller can see a fall back to decoding
   struct Restore { vaenmf_plan* p; bool v; ~Restore() { p->store_on = v; } } restore{p, want};

@@ -1423,6 +1423,7 @@ int vn_launch_tchain(vaenmf_plan* p, const VnChainCall& cc, hipStream_t st) {
 
 extern "C" int vaenmf_rng_fill(vaenmf_plan* p, uint32_t call, int32_t S, float* eps_out, float* u_out, void* stream) {
   if (int e = check_bound(p)) return e;
+  if (p->wide) return vn_launch_wide_rng_fill(p, call, S, eps_out, u_out, (hipStream_t)stream);    // [S][NT][128], 32 quads per frame
   hipLaunchKernelGGL(rng_fill_kernel, dim3(p->n_tiles), dim3(8 * p->tile_frames), 0, (hipStream_t)stream, p->d_tile_utt, p->d_tile_n0,
                      p->d_tile_cnt, p->d_frame_off, p->d_utt_seed, call, S, p->NT, eps_out, u_out);
   VN_CHECK_HIP(hipGetLastError());
@@ -1431,6 +1432,8 @@ extern "C" int vaenmf_rng_fill(vaenmf_plan* p, uint32_t call, int32_t S, float* 
 
 extern "C" int vaenmf_decode(vaenmf_plan* p, const float* Zs, int32_t Rcap, int32_t R, const float* B1, float* Vs_out, void* stream) {
   if (int e = check_bound(p)) return e;
+  VN_REQUIRE(!p->wide, "%s: a wide decoder plan (z_dim > 32 or a hidden layer of 256 units) has no decoding kernels; run the chain with the sample "
+             "store on (vaenmf_sample_store) and use vaenmf_m_step_stored / vaenmf_wiener_stored (vaenmf_sample_store_gather for the variances)", "vaenmf_decode");
   VN_REQUIRE(R >= 1 && R <= Rcap, "bad R=%d (Rcap=%d)", R, Rcap);
   DecodeArgs a = base_decode_args(p, Zs, Rcap, R, B1);
   a.Vs_out = Vs_out;
@@ -1442,6 +1445,8 @@ extern "C" int vaenmf_decode(vaenmf_plan* p, const float* Zs, int32_t Rcap, int3
 extern "C" int vaenmf_m_step(vaenmf_plan* p, const float* X2, float* W, float* Ht, float* g, const float* Zs,
                              int32_t Rcap, int32_t R, const float* B1, double* cost_frames, void* stream) {
   if (int e = check_bound(p)) return e;
+  VN_REQUIRE(!p->wide, "%s: a wide decoder plan (z_dim > 32 or a hidden layer of 256 units) has no decoding kernels; run the chain with the sample "
+             "store on (vaenmf_sample_store) and use vaenmf_m_step_stored / vaenmf_wiener_stored (vaenmf_sample_store_gather for the variances)", "vaenmf_m_step");
   VN_REQUIRE(R >= 1 && R <= Rcap, "bad R=%d (Rcap=%d)", R, Rcap);
   hipStream_t st = (hipStream_t)stream;
   DecodeArgs a = base_decode_args(p, Zs, Rcap, R, B1);
@@ -1464,6 +1469,8 @@ extern "C" int vaenmf_wiener(vaenmf_plan* p, const float* X2, const float* W, co
                              const float* Zs, int32_t Rcap, int32_t R, const float* B1, const float* X,
                              float* S_hat, float* N_hat, float* WFs, float* WFn, void* stream) {
   if (int e = check_bound(p)) return e;
+  VN_REQUIRE(!p->wide, "%s: a wide decoder plan (z_dim > 32 or a hidden layer of 256 units) has no decoding kernels; run the chain with the sample "
+             "store on (vaenmf_sample_store) and use vaenmf_m_step_stored / vaenmf_wiener_stored (vaenmf_sample_store_gather for the variances)", "vaenmf_wiener");
   VN_REQUIRE(R >= 1 && R <= Rcap, "bad R=%d (Rcap=%d)", R, Rcap);
   DecodeArgs a = base_decode_args(p, Zs, Rcap, R, B1);
   a.X2 = X2; a.W = W; a.Ht = const_cast<float*>(Ht); a.g = const_cast<float*>(g); a.X = X;

@@ -101,10 +101,13 @@ int upload(T* dst, const T* src, size_t n) {
 
 extern "C" int vaenmf_plan_create(const vaenmf_config* cfg, vaenmf_plan** out) {
   VN_REQUIRE(cfg && out, "null argument");
-  // decoder shapes: z(32 or 16) -> 128 [-> 128] -> F.  Latent dimension 16 runs the 32-wide first layer with zero padding
-  // (no random-walk noise on the padding); H2 = 0 is a decoder with ONE hidden layer (the reference's h_dim = [128]).
-  VN_REQUIRE(cfg->L == LAT || cfg->L == 16, "this build supports latent dims %d and 16 (got %d)", LAT, cfg->L);
-  VN_REQUIRE(cfg->H1 == HID && (cfg->H2 == HID || cfg->H2 == 0), "this build supports hidden sizes %d[,%d] (got %d,%d)", HID, HID, cfg->H1, cfg->H2);
+  // decoder shapes: z(16 | 32 | 64 | 128) -> 128 [-> 128] -> F, z -> 128 -> 256 -> F (the reference's h_dim = [256, 128]: the
+  // decoder runs over reversed(h_dim), models.py:133) and z -> 256 -> 128 -> F.  H2 = 0 is a decoder with ONE hidden layer
+  // (h_dim = [128]).  Narrow plans (L <= 32, no 256-wide layer) keep the latents in 32 columns, wide plans (wide.hip) in
+  // 128; columns beyond L are zero padding (no random-walk noise on them).
+  VN_REQUIRE(cfg->L == 16 || cfg->L == 32 || cfg->L == 64 || cfg->L == 128, "latent dim %d: this build runs z_dim 16, 32, 64 or 128", cfg->L);
+  VN_REQUIRE((cfg->H1 == HID && (cfg->H2 == 0 || cfg->H2 == HID || cfg->H2 == 256)) || (cfg->H1 == 256 && cfg->H2 == HID),
+             "decoder hidden sizes (%d, %d): this build runs (128), (128, 128), (128, 256) and (256, 128)", cfg->H1, cfg->H2);
   VN_REQUIRE(cfg->F >= 1 && cfg->F <= 640, "F=%d out of range (1..640)", cfg->F);
   VN_REQUIRE(cfg->K >= 1 && cfg->K <= 32, "NMF rank K=%d out of range (1..32)", cfg->K);
   VN_REQUIRE(cfg->max_frames >= 1 && cfg->max_utts >= 1, "bad capacities");
@@ -133,6 +136,11 @@ extern "C" int vaenmf_plan_create(const vaenmf_config* cfg, vaenmf_plan** out) {
   p->Dy = 0;
   p->Lz = cfg->L;
   p->one_hidden = cfg->H2 == 0;
+  p->wide = cfg->L > LAT || cfg->H1 != HID || cfg->H2 > HID;
+  p->Lp = p->wide ? 128 : LAT;
+  // fragment counts: a wide plan packs W1 over 4 k-steps of latents, W2 [H2/16][H1/32], W3 [Fs/16][last hidden layer / 32]
+  const size_t H1 = cfg->H1, H2 = cfg->H2 ? cfg->H2 : HID, Hlast = cfg->H2 ? cfg->H2 : cfg->H1;
+  const size_t nk1 = p->Lp / 32, nt3 = p->wide ? p->Fs / 16 : p->NT3;
   p->have_weights = false;
   p->Vb_ext = nullptr;
   p->store_on = false; p->VsS = nullptr; p->src = nullptr; p->VsS_cap = p->src_cap = 0; p->store_R = p->store_Rs = 0;
@@ -147,11 +155,11 @@ extern "C" int vaenmf_plan_create(const vaenmf_config* cfg, vaenmf_plan** out) {
   const size_t NTc = cfg->max_frames, Uc = cfg->max_utts;
   const size_t max_tiles = NTc / 32 + Uc + 1;
   int e = 0;
-  e |= dev_alloc(&p->w1f, (size_t)(HID / 16) * 1 * 2 * 64 * 8);
-  e |= dev_alloc(&p->w2f, (size_t)(HID / 16) * (HID / 32) * 2 * 64 * 8);
-  e |= dev_alloc(&p->w3f, (size_t)p->NT3 * (HID / 32) * 2 * 64 * 8);
-  e |= dev_alloc(&p->b1, HID);
-  e |= dev_alloc(&p->b2, HID);
+  e |= dev_alloc(&p->w1f, (H1 / 16) * nk1 * 2 * 64 * 8);
+  e |= dev_alloc(&p->w2f, (H2 / 16) * (H1 / 32) * 2 * 64 * 8);
+  e |= dev_alloc(&p->w3f, nt3 * (Hlast / 32) * 2 * 64 * 8);
+  e |= dev_alloc(&p->b1, H1);
+  e |= dev_alloc(&p->b2, H2);
   e |= dev_alloc(&p->b3, p->Fs);
   e |= dev_alloc(&p->w3n, HID);
   e |= dev_alloc(&p->w3c, (size_t)p->NT3c * (HID / 32) * 2 * 64 * 8);
@@ -216,8 +224,51 @@ extern "C" int vaenmf_plan_query(const vaenmf_plan* p, int32_t what) {
     case VAENMF_Q_DEV_ALLOCS: return (int)g_vn_dev_allocs;
     case VAENMF_Q_W_FUSED: return p->last_w_fused;
     case VAENMF_Q_CHAIN_KERNEL: return p->last_chain_kernel;
+    case VAENMF_Q_LP: return p->Lp;
     default: return -1;
   }
+}
+
+// The weights of a wide plan for wide.hip's kernel: W1 [H1/16 tiles][4 k-steps over the 128 latent columns, zero beyond L],
+// W2 [H2/16][H1/32], W3 [Fs/16][last hidden layer / 32] with every bin on the tiles (padding rows 0, b3 = -200: Vs = 0),
+// scaled like the narrow ones.
+static int set_weights_wide(vaenmf_plan* p, const float* W1, int in1, const float* b1, const float* W2, const float* b2,
+                            const float* W3, const float* b3) {
+  const int Lz = p->Lz, H1 = p->cfg.H1, H2 = p->cfg.H2, HL = H2 ? H2 : H1, F = p->cfg.F, Dy = in1 - Lz;
+  const double C2 = 2.0 * 1.4426950408889634, C1 = 1.4426950408889634;
+  auto scaled = [](const float* src, size_t n, double c) {
+    std::vector<float> v(n);
+    for (size_t i = 0; i < n; ++i) v[i] = (float)((double)src[i] * c);
+    return v;
+  };
+  const std::vector<float> W1s = scaled(W1, (size_t)H1 * in1, C2), b1s = scaled(b1, H1, C2);
+  const std::vector<float> W3s = scaled(W3, (size_t)F * HL, C1), b3s = scaled(b3, F, C1);
+  int e = 0;
+  const std::vector<uint16_t> f1 = pack_weights(W1s.data(), H1, Lz, in1, H1 / 16, p->Lp / 32);     // (the label columns stay out)
+  e |= upload((uint16_t*)p->w1f, f1.data(), f1.size());
+  e |= upload(p->b1, b1s.data(), (size_t)H1);
+  if (!p->one_hidden) {
+    const std::vector<float> W2s = scaled(W2, (size_t)H2 * H1, C2), b2s = scaled(b2, H2, C2);
+    const std::vector<uint16_t> f2 = pack_weights(W2s.data(), H2, H1, H1, H2 / 16, H1 / 32);
+    e |= upload((uint16_t*)p->w2f, f2.data(), f2.size());
+    e |= upload(p->b2, b2s.data(), (size_t)H2);
+  }
+  const std::vector<uint16_t> f3 = pack_weights(W3s.data(), F, HL, HL, p->Fs / 16, HL / 32);
+  std::vector<float> b3p(p->Fs, -200.f);
+  memcpy(b3p.data(), b3s.data(), sizeof(float) * F);
+  e |= upload((uint16_t*)p->w3f, f3.data(), f3.size());
+  e |= upload(p->b3, b3p.data(), b3p.size());
+  if (p->w1y) { (void)hipFree(p->w1y); p->w1y = nullptr; }
+  p->Dy = Dy;
+  if (Dy > 0) {                                // label columns of W1, [H1][Dy]
+    std::vector<float> wy((size_t)H1 * Dy);
+    for (int h = 0; h < H1; ++h) memcpy(&wy[(size_t)h * Dy], W1s.data() + (size_t)h * in1 + Lz, sizeof(float) * Dy);
+    e |= dev_alloc(&p->w1y, wy.size());
+    if (!e) e |= upload(p->w1y, wy.data(), wy.size());
+  }
+  if (e) return -2;
+  p->have_weights = true;
+  return 0;
 }
 
 extern "C" int vaenmf_set_decoder_weights(vaenmf_plan* p, const float* W1, int32_t in1, const float* b1, const float* W2,
@@ -226,6 +277,7 @@ extern "C" int vaenmf_set_decoder_weights(vaenmf_plan* p, const float* W1, int32
   VN_REQUIRE(p->one_hidden || (W2 && b2), "null second-layer weights (plan with H2 = %d)", p->cfg.H2);
   const int Lz = p->Lz;
   VN_REQUIRE(in1 >= Lz, "decoder input width %d < latent dim %d", in1, Lz);
+  if (p->wide) return set_weights_wide(p, W1, in1, b1, W2, b2, W3, b3);
   const int F = p->cfg.F;
   // first layer on the 32-wide MFMA k-step: [H][32 latent columns (zero beyond Lz) | Dy label columns]
   std::vector<float> W1pad;
@@ -391,7 +443,7 @@ extern "C" int vaenmf_layer1_bias(vaenmf_plan* p, const float* y, int32_t Dy, fl
   VN_REQUIRE(p && y && B1, "null argument");
   VN_REQUIRE(p->have_weights && p->NT > 0, "plan needs weights and a bound batch");
   VN_REQUIRE(Dy == p->Dy && Dy > 0, "label width %d does not match decoder input (L+%d)", Dy, p->Dy);
-  return vaenmf_dense(y, p->NT, Dy, Dy, p->w1y, p->b1, HID, VAENMF_ACT_NONE, B1, HID, stream);
+  return vaenmf_dense(y, p->NT, Dy, Dy, p->w1y, p->b1, p->cfg.H1, VAENMF_ACT_NONE, B1, p->cfg.H1, stream);
 }
 
 // Per-kernel timing: HIP events recorded on the launch stream around every hot-path

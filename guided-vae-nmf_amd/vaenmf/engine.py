@@ -40,9 +40,38 @@ def decoder_params_from_state(sd, prefix="decoder."):
     if n == 1:            # h_dim = [128] (scripts/evaluate_M1.py:44-85 lists such checkpoints): [W1, b1, W3, b3]
         return [get("hidden.0.weight"), get("hidden.0.bias"), get("reconstruction.weight"), get("reconstruction.bias")]
     if n != 2:
-        raise NotImplementedError("this build runs decoders with 1 or 2 hidden layers of 128 units (got %d layers)" % n)
+        raise NotImplementedError("this build runs decoders with 1 or 2 hidden layers (%s); got %d layers" % (_SHAPES_TEXT, n))
     return [get("hidden.0.weight"), get("hidden.0.bias"), get("hidden.1.weight"), get("hidden.1.bias"),
             get("reconstruction.weight"), get("reconstruction.bias")]
+
+
+Z_DIMS = (16, 32, 64, 128)
+HIDDEN = ((128, 0), (128, 128), (128, 256), (256, 128))      # decoder.hidden.0 / .1 widths; 0: one hidden layer
+_SHAPES_TEXT = ("z_dim 16, 32, 64 or 128 and decoder layers z -> 128 -> F, z -> 128 -> 128 -> F, z -> 128 -> 256 -> F (h_dim "
+                "[256, 128]: the decoder runs over reversed(h_dim)) or z -> 256 -> 128 -> F (h_dim [128, 256])")
+
+
+def decoder_shape(decoder, z_dim):
+    """(L, Lp, H1, H2, wide) of a decoder [W1, b1, (W2, b2,) W3, b3] (arrays or anything with .shape) and its latent
+    dimension, or NotImplementedError for a shape the library has no kernel for.  H1 / H2 are the widths of the decoder's
+    own first / second hidden layer (H2 = 0: one hidden layer).  wide: L > 32 or a 256-wide layer -- Lp = 128 latent
+    columns, the chain is the wide kernel and M-step / Wiener filter stream the sample store; narrow plans keep Lp = 32.
+    Pure: needs neither the library nor a GPU."""
+    shp = [tuple(int(v) for v in (a.shape if hasattr(a, "shape") else np.shape(a))) for a in decoder]
+    if len(shp) not in (4, 6):
+        raise NotImplementedError("this build runs decoders with 1 or 2 hidden layers (%s); got %d hidden layers"
+                                  % (_SHAPES_TEXT, len(shp) // 2 - 1))
+    L = int(z_dim)
+    if L not in Z_DIMS:
+        raise NotImplementedError("latent dim %d: this build runs %s" % (L, _SHAPES_TEXT))
+    H1, H2 = shp[0][0], (shp[2][0] if len(shp) == 6 else 0)
+    if (H1, H2) not in HIDDEN:
+        raise NotImplementedError("decoder hidden layers %s: this build runs %s" % ((H1, H2) if H2 else (H1,), _SHAPES_TEXT))
+    last = H2 or H1
+    if (len(shp) == 6 and shp[2] != (H2, H1)) or len(shp[-2]) != 2 or shp[-2][1] != last or shp[0][1] < L:
+        raise NotImplementedError("inconsistent decoder layer shapes %s for z_dim %d" % (shp[::2], L))
+    wide = L > LAT or 256 in (H1, H2)
+    return L, (128 if wide else LAT), H1, H2, wide
 
 
 def classifier_layers_from_state(sd, two_classes=False, bn_eps=1e-5):
@@ -79,38 +108,37 @@ def latent_dim_from_state(sd):
 
 class BatchEngine:
     def __init__(self, F, K, decoder, precision="bf16x3", device="cuda:0", max_frames=1 << 16, max_utts=256, z_dim=LAT):
-        """decoder = [W1 (H,L+Dy), b1, W2 (H,H), b2, W3 (F,H), b3] float32 numpy (nn.Linear layout), or [W1, b1, W3, b3]
-        for a decoder with one hidden layer (h_dim = [128]).  z_dim = L: 32 or 16 (16 runs on the 32-wide first layer with
-        zero padding: Z / Zs keep 32 columns, the last 16 stay zero)."""
+        """decoder = [W1 (H1,L+Dy), b1, W2 (H2,H1), b2, W3 (F,H2), b3] float32 numpy (nn.Linear layout), or [W1, b1, W3, b3]
+        for a decoder with one hidden layer (h_dim = [128]); the shapes decoder_shape accepts.  z_dim = L.  Z / Zs / the
+        replay draws keep self.Lp columns (32; 128 on a wide engine), zero beyond L.  A wide engine (self.wide) keeps the
+        sample-variance store on: its m_step / wiener / decode stream the store of the last chain."""
         if not torch.cuda.is_available():
             raise RuntimeError("vaenmf needs a ROCm GPU (MI355X); there is no CPU path")
         self.device = torch.device(device)
         torch.cuda.set_device(self.device)
         dec = [_np32(a) for a in decoder]
+        self.L, self.Lp, self.H1, self.H2, self.wide = decoder_shape(dec, z_dim)      # raises for what has no kernel
         if len(dec) == 4:
             W1, b1, W3, b3 = dec
             W2 = b2 = None
         else:
             W1, b1, W2, b2, W3, b3 = dec
-        if W1.shape[0] != HID or (W2 is not None and W2.shape != (HID, HID)) or W3.shape != (F, HID):
-            raise NotImplementedError("this build runs decoders z(32|16)+y -> %d [-> %d] -> F; got %s %s %s"
-                                      % (HID, HID, W1.shape, None if W2 is None else W2.shape, W3.shape))
-        if int(z_dim) not in (16, LAT):
-            raise NotImplementedError("latent dim %d: this build supports 16 and %d (z_dim 128 would need 4 k-steps in the "
-                                      "first layer and 128 latents per frame in registers)" % (z_dim, LAT))
-        self.F, self.K, self.L = int(F), int(K), int(z_dim)
+        if W3.shape[0] != F:
+            raise NotImplementedError("the decoder's output layer has %d rows, not F = %d" % (W3.shape[0], F))
+        self.F, self.K = int(F), int(K)
         self.Dy = W1.shape[1] - self.L
         if self.Dy < 0:
             raise NotImplementedError("first decoder layer has %d inputs, fewer than the latent dim %d" % (W1.shape[1], self.L))
         self.precision = {"bf16x3": _lib.PREC_BF16X3, "bf16": _lib.PREC_BF16}[precision]
         self._max_frames, self._max_utts = int(max_frames), int(max_utts)
-        cfg = _lib.Config(self.F, self.K, self.L, HID, HID if W2 is not None else 0, int(max_frames), int(max_utts), self.precision)
+        cfg = _lib.Config(self.F, self.K, self.L, self.H1, self.H2, int(max_frames), int(max_utts), self.precision)
         self._plan = C.c_void_p()
         check(lib().vaenmf_plan_create(C.byref(cfg), C.byref(self._plan)))
         check(lib().vaenmf_set_decoder_weights(self._plan, W1.ctypes.data, W1.shape[1], b1.ctypes.data, None if W2 is None else W2.ctypes.data,
                                                None if b2 is None else b2.ctypes.data, W3.ctypes.data, b3.ctypes.data))
         self.Fs = lib().vaenmf_plan_query(self._plan, _lib.Q_FS)
         self.Kp = lib().vaenmf_plan_query(self._plan, _lib.Q_KP)
+        assert lib().vaenmf_plan_query(self._plan, _lib.Q_LP) == self.Lp
         self.NT = 0
         self.B1 = None
 
@@ -146,8 +174,8 @@ class BatchEngine:
             self._bW = torch.empty(MU, Fs, Kp, device=dev, dtype=f32)
             self._bHt = torch.empty(MF, Kp, device=dev, dtype=f32)
             self._bg = torch.empty(MF, device=dev, dtype=f32)
-            self._bZ = torch.empty(MF, LAT, device=dev, dtype=f32)
-            self._bZs = torch.empty(MF, self.Rcap, LAT, device=dev, dtype=f32)
+            self._bZ = torch.empty(MF, self.Lp, device=dev, dtype=f32)
+            self._bZs = torch.empty(MF, self.Rcap, self.Lp, device=dev, dtype=f32)
             self._bcost = torch.empty(MF, device=dev, dtype=torch.float64)
             self._bS = torch.empty(MF, Fs, 2, device=dev, dtype=f32)      # outputs of run(): fixed addresses, so that a repeated
             self._bN = torch.empty(MF, Fs, 2, device=dev, dtype=f32)      # call has the signature vaenmf_em_run replays as a graph
@@ -169,6 +197,8 @@ class BatchEngine:
             cache[key] = (torch.from_numpy(self.frame_off.copy()).to(dev),
                           torch.repeat_interleave(torch.arange(self.U, dtype=torch.int32), torch.tensor(fc)).to(dev))
         self.d_frame_off, self.d_frame_utt = cache[key]
+        if self.wide:           # M-step and Wiener filter of a wide engine exist in their stored forms only
+            self.sample_store(True)
         return self
 
     def utt_slice(self, u):
@@ -241,9 +271,9 @@ class BatchEngine:
             h = self.dense(h, t(w), t(b), _lib.ACT_TANH)
         w, b = enc[-1]
         mu = self.dense(h, t(w), t(b), _lib.ACT_NONE)        # (NT, L)
-        if self.L == LAT:
+        if self.L == self.Lp:
             self.Z.copy_(mu)
-        else:                                                 # latent dimension 16: columns 16..31 are the zero padding
+        else:                                                 # columns L..Lp-1 are the zero padding
             self.Z.zero_()
             self.Z[:, :self.L].copy_(mu)
 
@@ -283,7 +313,7 @@ class BatchEngine:
             raise ValueError("decoder has no label input")
         y = y.to(self.device, torch.float32).contiguous()
         if getattr(self, "_bB1", None) is None:           # fixed address from batch to batch (vaenmf_em_run's graph signature)
-            self._bB1 = torch.empty(self._max_frames, HID, device=self.device, dtype=torch.float32)
+            self._bB1 = torch.empty(self._max_frames, self.H1, device=self.device, dtype=torch.float32)
         self.B1 = self._bB1[:self.NT]
         check(lib().vaenmf_layer1_bias(self._plan, _ptr(y), self.Dy, _ptr(self.B1), _stream()))
 
@@ -294,31 +324,38 @@ class BatchEngine:
         check(lib().vaenmf_mh_chain(self._plan, _ptr(self.X2), _ptr(self.W), _ptr(self.Ht), _ptr(self.g), _ptr(self.Z),
                                     int(bool(update_Z)), _ptr(self.B1), _ptr(self.Zs), self.Rcap, int(nsamples), int(burnin), float(var_rw),
                                     C.byref(rng), _ptr(acc), _stream()))
+        self._store_R = int(nsamples)
         return acc
 
     def sample_store(self, on=True):
         """Keep the decoded variances of the chain's samples in HBM (see include/vaenmf.h); sized here, for the
         bound batch and chains of up to Rcap samples per frame (vaenmf_mh_chain itself never allocates)."""
-        check(lib().vaenmf_sample_store(self._plan, int(self.Rcap) if on else 0))
+        check(lib().vaenmf_sample_store(self._plan, int(self.Rcap) if (on or self.wide) else 0))
 
     def stored_variances(self, R):
         """Vs of the last chain's samples from the store: device float32 [NT,R,Fs]."""
+        if getattr(self, "_store_R", R) != R:
+            raise ValueError("the store holds %d samples per frame (the last chain's), not %d" % (self._store_R, R))
         out = torch.empty(self.NT, R, self.Fs, device=self.device, dtype=torch.float32)
         check(lib().vaenmf_sample_store_gather(self._plan, _ptr(out), _stream()))
         return out
 
     def rng_fill(self, call, S):
-        eps = torch.empty(S, self.NT, LAT, device=self.device, dtype=torch.float32)
+        eps = torch.empty(S, self.NT, self.Lp, device=self.device, dtype=torch.float32)
         u = torch.empty(S, self.NT, device=self.device, dtype=torch.float32)
         check(lib().vaenmf_rng_fill(self._plan, int(call), int(S), _ptr(eps), _ptr(u), _stream()))
         return eps, u
 
     def decode(self, R):
+        if self.wide:           # the variances of the last chain's samples, from its store
+            return self.stored_variances(R)
         Vs = torch.empty(self.NT, R, self.Fs, device=self.device, dtype=torch.float32)
         check(lib().vaenmf_decode(self._plan, _ptr(self.Zs), self.Rcap, int(R), _ptr(self.B1), _ptr(Vs), _stream()))
         return Vs
 
     def m_step(self, R):
+        if self.wide:
+            return self.m_step_stored()
         check(lib().vaenmf_m_step(self._plan, _ptr(self.X2), _ptr(self.W), _ptr(self.Ht), _ptr(self.g), _ptr(self.Zs),
                                   self.Rcap, int(R), _ptr(self.B1), _ptr(self.cost_frames), _stream()))
         return self.cost_frames
@@ -339,6 +376,8 @@ class BatchEngine:
         return S, N, WFs, WFn
 
     def wiener(self, R, want_masks=False):
+        if self.wide:
+            return self.wiener_stored(want_masks)
         S = torch.empty_like(self.X)
         N = torch.empty_like(self.X)
         WFs = torch.empty_like(self.X2) if want_masks else None
@@ -357,13 +396,14 @@ class BatchEngine:
         cost = self._bcu[int(niter)][:self.U * int(niter)].view(self.U, int(niter))
         cost.zero_()
         S, N = self._bS[:self.NT], self._bN[:self.NT]
-        if store is None:       # the chain keeps the samples' variances in HBM, M-step and Wiener filter stream them
+        if store is None or self.wide:       # the chain keeps the samples' variances in HBM, M-step and Wiener filter stream them
             store = True
         self.sample_store(store)
         check(lib().vaenmf_em_run(self._plan, _ptr(self.X2), _ptr(self.W), _ptr(self.Ht), _ptr(self.g), _ptr(self.Z),
                                   _ptr(self.B1), _ptr(self.Zs), self.Rcap, int(niter), int(nsE), int(biE), int(nsWF),
                                   int(biWF), float(var_rw), _ptr(self.X), _ptr(S), _ptr(N), _ptr(cost), _stream()))
-        self.sample_store(False)
+        self._store_R = int(nsWF)
+        self.sample_store(False)                       # (a wide engine keeps it on)
         return cost.clone(), S.clone(), N.clone()      # (the buffers are overwritten by the next run)
 
     # ------------------------------------------------------------------ host views (reference shapes)

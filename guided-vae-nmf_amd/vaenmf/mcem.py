@@ -14,7 +14,7 @@ steps, Wiener chain = burnin_WF samples after 30."""
 import numpy as np
 import torch
 
-from .engine import BatchEngine, decoder_params_from_state, LAT
+from .engine import BatchEngine, decoder_params_from_state, Z_DIMS
 
 
 def _state(vae):
@@ -84,8 +84,8 @@ class _MCEM:
         dev = torch.device(device if device not in (None, "cpu") else "cuda:0")
         N, F = X.shape
         L = getattr(vae, "latent_dim", None) or getattr(vae, "z_dim")
-        if L not in (16, LAT):
-            raise NotImplementedError("latent dim %d: this build supports 16 and %d" % (L, LAT))
+        if L not in Z_DIMS:
+            raise NotImplementedError("latent dim %d: this build runs z_dim %s" % (L, ", ".join(str(v) for v in Z_DIMS)))
         self._L = L
         ns_e, _ = self.e_step_counts()
         ns_w, _ = self.wf_counts()
@@ -160,7 +160,7 @@ class _MCEM:
         if self.rng == "replay":
             S = nsamples + burnin
             L = self._L
-            e = torch.zeros(S, N, LAT)                                         # (latent dim 16: columns 16..31 stay zero)
+            e = torch.zeros(S, N, eng.Lp)                                      # (columns L..Lp-1 stay zero)
             uu = torch.empty(S, N)
             for m in range(S):                                                 # mcem.py:407, :420
                 e[m, :, :L] = torch.randn(L, N).T

@@ -29,8 +29,9 @@
  *   W   float  [U][Fs][Kp] NMF dictionary per utterance        (mcem.py:48)  pad = 0
  *   Ht  float  [NT][Kp]   NMF activations, transposed          (mcem.py:49)  pad = 0
  *   g   float  [NT]       per-frame gain                       (mcem.py:51)
- *   Z   float  [NT][L]    last draw of the latent variables    (mcem.py:368, transposed)
- *   Zs  float  [NT][Rcap][L] posterior samples                 (mcem.py:386)
+ *   Lp  = 32, or 128 on a wide plan (query VAENMF_Q_LP)    latent row stride; columns L..Lp-1 are zero
+ *   Z   float  [NT][Lp]   last draw of the latent variables    (mcem.py:368, transposed)
+ *   Zs  float  [NT][Rcap][Lp] posterior samples                (mcem.py:386)
  *   B1  float  [NT][H1]   per-frame first-layer bias b1 + W1[:,L:] y_n  (M2: the label
  *                         part of decoder(cat([Z,y])) folded once, mcem.py:242); NULL = M1
  */
@@ -58,7 +59,9 @@ enum { VAENMF_Q_FS = 0, VAENMF_Q_KP = 1, VAENMF_Q_TILES = 2, VAENMF_Q_NT = 3, VA
        VAENMF_Q_W_FUSED = 9,     /* 1 when the last stored M-step ran the W statistics fused with the W update's sums over frames
                                     (2: per 16-frame group, the small-batch form; the same bits) */
        VAENMF_Q_CHAIN_KERNEL = 10, /* kernel of the last MH chain: 0 = team kernel (64-bit addresses), 1 = one wavefront per 16 frames,
-                                      2 = four wavefronts per 16 frames (bench shape, batches of at most one wave tile per CU) */
+                                      2 = four wavefronts per 16 frames (bench shape, batches of at most one wave tile per CU),
+                                      3 = the wide-decoder kernel (a workgroup of four wavefronts per 16 frames; wide plans only) */
+       VAENMF_Q_LP = 11,         /* latent columns Lp of Z, Zs and the replay draws: 32, or 128 on a wide plan (L > 32 or a hidden layer of 256) */
        VAENMF_Q_DEV_ALLOCS = 8 };/* device allocations the library has made in this process so far (any plan): a caller that
                                     reuses a plan can check that a call allocated nothing */
 
@@ -69,8 +72,12 @@ typedef struct {
   int32_t F;          /* frequency bins, n_fft/2+1: any value in 1..640 (n_fft need not be a power of two; padding bins
                          F..Fs-1 of every output are zero)                          */
   int32_t K;          /* NMF rank (<= 32)                                           */
-  int32_t L;          /* latent dimension (this build: 32)                          */
-  int32_t H1, H2;     /* decoder hidden sizes, first and second layer (this build: 128,128) */
+  int32_t L;          /* latent dimension: 16, 32, 64 or 128                        */
+  int32_t H1, H2;     /* decoder hidden sizes, first and second layer (decoder.hidden.0 / .1, which the reference builds over
+                         reversed(h_dim), models.py:133): (128,128), (128,0) = one hidden layer, (128,256) = h_dim [256,128],
+                         (256,128) = h_dim [128,256].  A plan with L > 32 or a 256-wide layer is WIDE: Lp = 128 latent columns,
+                         the MH chain is the wide kernel, and the M-step / Wiener filter exist in their stored forms only (see
+                         vaenmf_sample_store)                                                                                */
   int32_t max_frames; /* capacity: total frames of a bound batch                    */
   int32_t max_utts;   /* capacity: utterances of a bound batch                      */
   int32_t precision;  /* VAENMF_PREC_*                                              */
@@ -79,7 +86,7 @@ typedef struct {
 typedef struct {
   int32_t  mode;        /* VAENMF_RNG_*                                             */
   uint32_t call;        /* chain-invocation counter (EM iteration index; WF = niter) */
-  const float* eps;     /* DEV [S][NT][L] N(0,1) draws, step-major   (REPLAY only; mcem.py:407) */
+  const float* eps;     /* DEV [S][NT][Lp] N(0,1) draws, step-major  (REPLAY only; mcem.py:407) */
   const float* u;       /* DEV [S][NT]    U(0,1) draws               (REPLAY only; mcem.py:420) */
 } vaenmf_rng;
 
@@ -147,12 +154,14 @@ int vaenmf_mh_chain(vaenmf_plan* p, const float* X2, const float* W, const float
 int vaenmf_wchain_addressable(int64_t NT, int32_t Rcap, int32_t steps, int32_t Fs, int32_t Kp, int32_t n_utt, int32_t replay);
 
 /* The draws the DEVICE generator hands to step s of chain invocation rng->call:
- * eps_out DEV [S][NT][L], u_out DEV [S][NT].  Test/debug aid: a REPLAY run fed with
- * these buffers is bit-identical to the DEVICE run. */
+ * eps_out DEV [S][NT][Lp], u_out DEV [S][NT].  Test/debug aid: a REPLAY run fed with
+ * these buffers is bit-identical to the DEVICE run.  (Lp / 4 streams of four latents per frame.) */
 int vaenmf_rng_fill(vaenmf_plan* p, uint32_t call, int32_t S, float* eps_out, float* u_out, void* stream);
 
 /* Vs = decoder(Z_samples): replaces compute_Vs (mcem.py:444-454 / :297-307).
- * Vs_out DEV [NT][R][Fs] (the reference's (R,F,N) tensor, frame-major). */
+ * Vs_out DEV [NT][R][Fs] (the reference's (R,F,N) tensor, frame-major).
+ * vaenmf_decode, vaenmf_m_step and vaenmf_wiener return an error on a wide plan: there the chain's sample store
+ * (vaenmf_sample_store, vaenmf_sample_store_gather, vaenmf_m_step_stored, vaenmf_wiener_stored) is the only path. */
 int vaenmf_decode(vaenmf_plan* p, const float* Zs, int32_t Rcap, int32_t R, const float* B1,
                   float* Vs_out, void* stream);
 
@@ -179,7 +188,8 @@ int vaenmf_wiener(vaenmf_plan* p, const float* X2, const float* W, const float* 
  * chain and filter.  cost DEV [n_utt][niter] double.  (nsE, biE) / (nsWF, biWF) are the
  * EFFECTIVE sample/burn-in counts (the caller applies MCEM_M1's positional-shift quirk,
  * mcem.py:461-462).  Device RNG only (rng_mode REPLAY is served step by step by the
- * calls above).
+ * calls above).  On a wide plan the sample store must be on (there is no decoding path); a batch
+ * whose store would not fit is an error, not a fall back.
  * A call whose signature (buffers, shapes, counts) repeats the previous call's is captured into a
  * HIP graph once and replayed from then on -- one launch per call instead of ~600; the batch's
  * contents (spectrogram, seeds, frame tables) sit behind the same pointers and are read at run
