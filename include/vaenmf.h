@@ -190,11 +190,15 @@ int vaenmf_wiener(vaenmf_plan* p, const float* X2, const float* W, const float* 
  * mcem.py:461-462).  Device RNG only (rng_mode REPLAY is served step by step by the
  * calls above).  On a wide plan the sample store must be on (there is no decoding path); a batch
  * whose store would not fit is an error, not a fall back.
- * A call whose signature (buffers, shapes, counts) repeats the previous call's is captured into a
- * HIP graph once and replayed from then on -- one launch per call instead of ~600; the batch's
- * contents (spectrogram, seeds, frame tables) sit behind the same pointers and are read at run
- * time.  Profiling (vaenmf_profile_*) and VAENMF_GRAPH=0 keep the launch-by-launch path;
- * results are the same either way. */
+ * A call signature (buffers, shapes, frame offsets, counts, var_rw, the kernel switches) runs launch
+ * by launch at its first appearance on a plan, is captured into a HIP graph at its second --
+ * whatever other calls came between -- and is replayed from then on: one launch per call instead
+ * of ~600.  A plan keeps four graphs (the least recently used one is dropped, and captured again
+ * when its signature returns) and remembers the last eight signatures it has run once; one that has
+ * been forgotten starts over with a launch-by-launch call.  The batch's contents (spectrogram,
+ * seeds, frame tables) sit behind the same pointers and are read at run time.  Profiling
+ * (vaenmf_profile_*) and VAENMF_GRAPH=0 keep the launch-by-launch path; results are the same
+ * either way. */
 int vaenmf_em_run(vaenmf_plan* p, const float* X2, float* W, float* Ht, float* g, float* Z,
                   const float* B1, float* Zs, int32_t Rcap, int32_t niter,
                   int32_t nsE, int32_t biE, int32_t nsWF, int32_t biWF, float var_rw,

@@ -518,6 +518,33 @@ def synth_utterance(seed, n_samples=64000, fs=16000):
 
 
 # ----------------------------------------------------------------------------
+# The library's counter-based NMF initialisation (vaenmf_init_nmf), restated
+# ----------------------------------------------------------------------------
+def splitmix64(x):
+    """One output of splitmix64 for the state(s) x (numpy uint64, any shape): the state advances by the golden-ratio
+    increment, then the two xor-shift-multiply rounds.  All arithmetic wraps modulo 2^64."""
+    with np.errstate(over="ignore"):
+        z = np.asarray(x, dtype=np.uint64) + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+
+
+def nmf_init_device(seed, salt, F, K, N, eps):
+    """W (F, K) and Ht (N, K) float32 of ONE utterance as vaenmf_init_nmf draws them (EM.init_parameters, mcem.py:42-44):
+    element (f, k) of W is u01(splitmix64(seed ^ salt ^ (0x57 << 56) ^ (f K + k))), element (k, n) of H -- n counted
+    inside the utterance -- u01(splitmix64(seed ^ salt ^ (0x48 << 56) ^ (n K + k))), u01 = the top 24 bits times 2^-24,
+    both clamped from below by the float32 eps.  Integer work and one exact conversion: comparable bit for bit."""
+    key = np.uint64(int(seed) & (2 ** 64 - 1)) ^ np.uint64(int(salt) & (2 ** 64 - 1))
+    u01 = lambda r: (r >> np.uint64(40)).astype(np.float32) * np.float32(2.0 ** -24)
+    idx_w = np.arange(F * K, dtype=np.uint64).reshape(F, K)
+    idx_h = np.arange(N * K, dtype=np.uint64).reshape(N, K)
+    W = np.maximum(u01(splitmix64(key ^ np.uint64(0x57 << 56) ^ idx_w)), np.float32(eps))
+    Ht = np.maximum(u01(splitmix64(key ^ np.uint64(0x48 << 56) ^ idx_h)), np.float32(eps))
+    return W, Ht
+
+
+# ----------------------------------------------------------------------------
 # Label / guide front-ends (python/processing/target.py)
 # ----------------------------------------------------------------------------
 def heavy_tailed_stft(F, N, seed):

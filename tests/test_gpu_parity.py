@@ -12,6 +12,8 @@ Stated tolerances (float32 unless noted):
     eng.stored_variances / eng.decode, both precision modes): W, H, g, the masks (absolute) and S_hat / N_hat (L2) within
     max(2e-5, 16 e32), the cost within max(1e-6, 16 e32), e32 being the float32 oracle's own error against float64.
   * label / SPP / mask / dense / Gram front-ends over shapes and edges: the rules in the docstring of tests/test_gpu_front_ends.py.
+  * the host driver (tests/test_gpu_em_driver.py: fused run, graph replay, rebinds, profiling against the step-by-step calls):
+    S_hat, N_hat, W, H, g, Z bit-equal; costs 1e-12 relative (the host sums the per-frame doubles in another order).
 """
 import os
 

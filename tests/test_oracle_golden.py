@@ -365,3 +365,29 @@ def test_classifier_batch_norm_and_two_class_forwards():
         return 1 / (1 + np.exp(-(h @ w.astype(np.float64).T + b)))
     assert np.max(np.abs(run(classifier_layers_from_state(pb)) - z["bn_y"])) < 2e-6
     assert np.max(np.abs(run(classifier_layers_from_state(p2, two_classes=True)) - z["c2_y"][:, 0, :])) < 2e-6
+
+
+def test_nmf_init_device_restatement():
+    """orc.nmf_init_device (the keying of vaenmf_init_nmf restated in numpy uint64; tests/test_gpu_em_driver.py holds the
+    kernel to it bit for bit): splitmix64 at two values worked out by hand -- the first two outputs of the generator
+    started at 0, which are also its published test vectors -- and every draw in [eps, 1) on the 2^-24 grid."""
+    assert int(orc.splitmix64(np.uint64(0))) == 0xE220A8397B1DCDAF
+    assert int(orc.splitmix64(np.uint64(0x9E3779B97F4A7C15))) == 0x6E789E6AA1B965F4
+    # element (0, 0) of W with seed ^ salt = 0x57 << 56 has key 0: the top 24 bits of the first value above
+    W, _ = orc.nmf_init_device(0x57 << 56, 0, 1, 1, 1, 1e-8)
+    assert W.shape == (1, 1) and W[0, 0] == np.float32(0xE220A8 * 2.0 ** -24)
+    for seed, salt, eps in ((5, 0, 1e-8), (2 ** 64 - 3, 0x9E3779B97F4A7C15, 1e-8), (7, 0xDEADBEEFCAFEF00D, 0.3)):
+        W, Ht = orc.nmf_init_device(seed, salt, 257, 9, 131, eps)
+        assert W.shape == (257, 9) and Ht.shape == (131, 9) and W.dtype == Ht.dtype == np.float32
+        for a in (W, Ht):
+            assert a.min() >= np.float32(eps) and a.max() < 1.0
+            free = a[a > np.float32(eps)].astype(np.float64) * 2.0 ** 24          # values the clamp left alone
+            assert np.array_equal(free, np.round(free))
+        if eps == 0.3:                                                             # the clamp acts (about 30 % of the draws)
+            assert 0.2 < np.mean(W == np.float32(0.3)) < 0.4 and 0.2 < np.mean(Ht == np.float32(0.3)) < 0.4
+        else:
+            assert 0.45 < W.mean() < 0.55 and 0.45 < Ht.mean() < 0.55
+        W2, Ht2 = orc.nmf_init_device(seed ^ 1, salt, 257, 9, 131, eps)
+        assert not np.array_equal(W, W2) and not np.array_equal(Ht, Ht2)
+        # W and H of one utterance are different streams (the tags 0x57 / 0x48)
+        assert not np.array_equal(W[:131], Ht)
