@@ -34,6 +34,22 @@
  *   Zs  float  [NT][Rcap][Lp] posterior samples                (mcem.py:386)
  *   B1  float  [NT][H1]   per-frame first-layer bias b1 + W1[:,L:] y_n  (M2: the label
  *                         part of decoder(cat([Z,y])) folded once, mcem.py:242); NULL = M1
+ *
+ * Supported value range
+ *   The chain's energy takes one logarithm and one reciprocal for two bins, log(Vx0 Vx1) and
+ *   (X2_0 Vx1 + X2_1 Vx0) / (Vx0 Vx1) with Vx = g Vs + (W H); the cost of the stored M-step does the same
+ *   for two sample rows of a bin; the M-step squares 1 / Vx (as the reference does).  Supported
+ *   are inputs for which every such product -- Vx of bins f and f + 2 of a group of four, Vx of
+ *   the same bin in neighbouring samples, |X|^2 of one bin times Vx of its partner, and Vx^2 --
+ *   is a normal float32, [2^-126, 2^128).  The range holds per PAIR, not per value: Vx = 1e-25
+ *   next to Vx = 1e5 is fine, two neighbours at 1e-20 are not.  With Vx and |X|^2 inside
+ *   [1e-19, 1.8e19] every pair is.  Outside it nothing is reported: v_rcp_f32 / v_log_f32 flush
+ *   denormals, a product that under- or overflows gives an infinite energy or inf - inf, and the
+ *   results of that frame -- from the next M-step on those of its utterance -- are non-finite or
+ *   wrong.  Utterances do not share sums: a non-finite
+ *   utterance leaves the others of its batch bit for bit as they are without it.  int16-scaled
+ *   audio at full scale (|X|^2 <= 2^48.6 at n_fft 1278, the longest window F <= 640 allows) and
+ *   audio at -80 dBFS with 80 dB of range inside a frame lie 2^10 and more inside.
  */
 #ifndef VAENMF_H
 #define VAENMF_H
