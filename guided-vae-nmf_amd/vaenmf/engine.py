@@ -153,6 +153,18 @@ class BatchEngine:
         except Exception:
             pass
 
+    def _empty(self, shape, dtype, name=None):
+        """Every device buffer the engine hands to the library comes from here (`name` says which one): a subclass can
+        place them elsewhere, as tests/guarded.py does to surround each with memory it inspects."""
+        return torch.empty(tuple(int(v) for v in shape), device=self.device, dtype=dtype)
+
+    def _wiener_outputs(self, want_masks):
+        f32 = torch.float32
+        S, N = self._empty((self.NT, self.Fs, 2), f32, "S_hat"), self._empty((self.NT, self.Fs, 2), f32, "N_hat")
+        if not want_masks:
+            return S, N, None, None
+        return S, N, self._empty((self.NT, self.Fs), f32, "WFs"), self._empty((self.NT, self.Fs), f32, "WFn")
+
     # ------------------------------------------------------------------ batch
     def bind(self, frame_counts, Rcap, seeds=None):
         fc = [int(n) for n in frame_counts]
@@ -169,16 +181,16 @@ class BatchEngine:
         # job alternates batches of 63 and 62 utterances.
         if getattr(self, "_cap_key", None) != self.Rcap:
             MF, MU = self._max_frames, self._max_utts
-            self._bX = torch.empty(MF, Fs, 2, device=dev, dtype=f32)      # complex64, interleaved
-            self._bX2 = torch.empty(MF, Fs, device=dev, dtype=f32)
-            self._bW = torch.empty(MU, Fs, Kp, device=dev, dtype=f32)
-            self._bHt = torch.empty(MF, Kp, device=dev, dtype=f32)
-            self._bg = torch.empty(MF, device=dev, dtype=f32)
-            self._bZ = torch.empty(MF, self.Lp, device=dev, dtype=f32)
-            self._bZs = torch.empty(MF, self.Rcap, self.Lp, device=dev, dtype=f32)
-            self._bcost = torch.empty(MF, device=dev, dtype=torch.float64)
-            self._bS = torch.empty(MF, Fs, 2, device=dev, dtype=f32)      # outputs of run(): fixed addresses, so that a repeated
-            self._bN = torch.empty(MF, Fs, 2, device=dev, dtype=f32)      # call has the signature vaenmf_em_run replays as a graph
+            self._bX = self._empty((MF, Fs, 2), f32, "X")                 # complex64, interleaved
+            self._bX2 = self._empty((MF, Fs), f32, "X2")
+            self._bW = self._empty((MU, Fs, Kp), f32, "W")
+            self._bHt = self._empty((MF, Kp), f32, "Ht")
+            self._bg = self._empty((MF,), f32, "g")
+            self._bZ = self._empty((MF, self.Lp), f32, "Z")
+            self._bZs = self._empty((MF, self.Rcap, self.Lp), f32, "Zs")
+            self._bcost = self._empty((MF,), torch.float64, "cost_frames")
+            self._bS = self._empty((MF, Fs, 2), f32, "run_S")             # outputs of run(): fixed addresses, so that a repeated
+            self._bN = self._empty((MF, Fs, 2), f32, "run_N")             # call has the signature vaenmf_em_run replays as a graph
             self._bcu = {}                                                # niter -> [max_utts, niter] float64
             self._cap_key = self.Rcap
         self.X, self.X2, self.W, self.Ht = self._bX[:NT], self._bX2[:NT], self._bW[:self.U], self._bHt[:NT]
@@ -236,7 +248,7 @@ class BatchEngine:
         """act(x w^T + b) on the device (models.py:101-104 / 57-62)."""
         M, inn = x.shape
         out = w.shape[0]
-        y = torch.empty(M, out, device=self.device, dtype=torch.float32)
+        y = self._empty((M, out), torch.float32, "dense")
         check(lib().vaenmf_dense(_ptr(x, rows_strided=True), M, inn, x.stride(0), _ptr(w), _ptr(b), out, act, _ptr(y), out, _stream()))
         return y
 
@@ -313,14 +325,14 @@ class BatchEngine:
             raise ValueError("decoder has no label input")
         y = y.to(self.device, torch.float32).contiguous()
         if getattr(self, "_bB1", None) is None:           # fixed address from batch to batch (vaenmf_em_run's graph signature)
-            self._bB1 = torch.empty(self._max_frames, self.H1, device=self.device, dtype=torch.float32)
+            self._bB1 = self._empty((self._max_frames, self.H1), torch.float32, "B1")
         self.B1 = self._bB1[:self.NT]
         check(lib().vaenmf_layer1_bias(self._plan, _ptr(y), self.Dy, _ptr(self.B1), _stream()))
 
     # ------------------------------------------------------------------ hot path
     def mh_chain(self, nsamples, burnin, var_rw, call=0, eps=None, u=None, want_acc=False, update_Z=True):
         rng = _lib.Rng(_lib.RNG_DEVICE if eps is None else _lib.RNG_REPLAY, int(call), _ptr(eps), _ptr(u))
-        acc = torch.empty(nsamples + burnin, self.NT, device=self.device, dtype=torch.float32) if want_acc else None
+        acc = self._empty((nsamples + burnin, self.NT), torch.float32, "acc") if want_acc else None
         check(lib().vaenmf_mh_chain(self._plan, _ptr(self.X2), _ptr(self.W), _ptr(self.Ht), _ptr(self.g), _ptr(self.Z),
                                     int(bool(update_Z)), _ptr(self.B1), _ptr(self.Zs), self.Rcap, int(nsamples), int(burnin), float(var_rw),
                                     C.byref(rng), _ptr(acc), _stream()))
@@ -336,20 +348,20 @@ class BatchEngine:
         """Vs of the last chain's samples from the store: device float32 [NT,R,Fs]."""
         if getattr(self, "_store_R", R) != R:
             raise ValueError("the store holds %d samples per frame (the last chain's), not %d" % (self._store_R, R))
-        out = torch.empty(self.NT, R, self.Fs, device=self.device, dtype=torch.float32)
+        out = self._empty((self.NT, R, self.Fs), torch.float32, "Vs")
         check(lib().vaenmf_sample_store_gather(self._plan, _ptr(out), _stream()))
         return out
 
     def rng_fill(self, call, S):
-        eps = torch.empty(S, self.NT, self.Lp, device=self.device, dtype=torch.float32)
-        u = torch.empty(S, self.NT, device=self.device, dtype=torch.float32)
+        eps = self._empty((S, self.NT, self.Lp), torch.float32, "eps")
+        u = self._empty((S, self.NT), torch.float32, "u")
         check(lib().vaenmf_rng_fill(self._plan, int(call), int(S), _ptr(eps), _ptr(u), _stream()))
         return eps, u
 
     def decode(self, R):
         if self.wide:           # the variances of the last chain's samples, from its store
             return self.stored_variances(R)
-        Vs = torch.empty(self.NT, R, self.Fs, device=self.device, dtype=torch.float32)
+        Vs = self._empty((self.NT, R, self.Fs), torch.float32, "Vs")
         check(lib().vaenmf_decode(self._plan, _ptr(self.Zs), self.Rcap, int(R), _ptr(self.B1), _ptr(Vs), _stream()))
         return Vs
 
@@ -367,10 +379,7 @@ class BatchEngine:
         return self.cost_frames
 
     def wiener_stored(self, want_masks=False):
-        S = torch.empty_like(self.X)
-        N = torch.empty_like(self.X)
-        WFs = torch.empty(self.NT, self.Fs, device=self.device, dtype=torch.float32) if want_masks else None
-        WFn = torch.empty(self.NT, self.Fs, device=self.device, dtype=torch.float32) if want_masks else None
+        S, N, WFs, WFn = self._wiener_outputs(want_masks)
         check(lib().vaenmf_wiener_stored(self._plan, _ptr(self.W), _ptr(self.Ht), _ptr(self.g), _ptr(self.X), _ptr(S), _ptr(N),
                                          _ptr(WFs), _ptr(WFn), _stream()))
         return S, N, WFs, WFn
@@ -378,10 +387,7 @@ class BatchEngine:
     def wiener(self, R, want_masks=False):
         if self.wide:
             return self.wiener_stored(want_masks)
-        S = torch.empty_like(self.X)
-        N = torch.empty_like(self.X)
-        WFs = torch.empty_like(self.X2) if want_masks else None
-        WFn = torch.empty_like(self.X2) if want_masks else None
+        S, N, WFs, WFn = self._wiener_outputs(want_masks)
         check(lib().vaenmf_wiener(self._plan, _ptr(self.X2), _ptr(self.W), _ptr(self.Ht), _ptr(self.g), _ptr(self.Zs),
                                   self.Rcap, int(R), _ptr(self.B1), _ptr(self.X), _ptr(S), _ptr(N), _ptr(WFs), _ptr(WFn), _stream()))
         return S, N, WFs, WFn
@@ -392,7 +398,7 @@ class BatchEngine:
         bf16x3 mode; vaenmf_em_run falls back to the decoding M-step when a batch's store would pass 3.5 GB --
         VAENMF_Q_MSTEP_PATH tells which path ran)."""
         if int(niter) not in self._bcu:
-            self._bcu[int(niter)] = torch.empty(self._max_utts * int(niter), device=self.device, dtype=torch.float64)
+            self._bcu[int(niter)] = self._empty((self._max_utts * int(niter),), torch.float64, "run_cost")
         cost = self._bcu[int(niter)][:self.U * int(niter)].view(self.U, int(niter))
         cost.zero_()
         S, N = self._bS[:self.NT], self._bN[:self.NT]

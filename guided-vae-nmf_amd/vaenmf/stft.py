@@ -81,8 +81,9 @@ def _opts(nfft, hop, center, pad_mode, window):
 
 
 def stft_batch(wav, sample_counts, fs, wlen_sec, hop_percent, Fs=None, device="cuda:0", win="hann", center=True,
-               pad_mode="reflect"):
-    """wav: device float32 [sum T] (utterances concatenated).  Returns (X [NT,Fs,2], frame_counts)."""
+               pad_mode="reflect", out=None):
+    """wav: device float32 [sum T] (utterances concatenated).  Returns (X [NT,Fs,2], frame_counts).
+    out: a callable (shape, dtype) -> dense device tensor that supplies X instead of torch.empty (as BatchEngine._empty)."""
     dev = torch.device(device)
     pm = _pad_mode(pad_mode)
     key = ("stft", tuple(int(t) for t in sample_counts), fs, wlen_sec, hop_percent, bool(center), str(dev))
@@ -102,7 +103,7 @@ def stft_batch(wav, sample_counts, fs, wlen_sec, hop_percent, Fs=None, device="c
     F = nfft // 2 + 1
     Fs = Fs or (F + 15) // 16 * 16
     NT = int(sum(fc))
-    X = torch.empty(NT, Fs, 2, device=dev, dtype=torch.float32)
+    X = torch.empty(NT, Fs, 2, device=dev, dtype=torch.float32) if out is None else out((NT, Fs, 2), torch.float32)
     opts = _opts(nfft, hop, center, pm, window)
     check(lib().vaenmf_stft_batch_ex(_ptr(wav), NT, _ptr(soff), _ptr(foff), _ptr(futt), _ptr(plen), C.byref(opts), Fs,
                                      _ptr(X), _stream()))

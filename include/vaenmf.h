@@ -15,7 +15,12 @@
  *   - `stream` is a hipStream_t passed as void* (0 = default stream).  All work is
  *     enqueued asynchronously; no call synchronises the device unless stated.
  *   - pointers marked DEV are device pointers owned by the caller (e.g. the
- *     PyTorch-ROCm allocator), 16-byte aligned, never freed by the callee.
+ *     PyTorch-ROCm allocator), never freed by the callee.  Required alignment: 16 bytes, and no more: the rows of X, X2,
+ *     Vb, W, Ht, Z, Zs, B1, the replay draws and every [..][Fs] output are read and written with 16-byte vector accesses,
+ *     and their row strides (Fs, Kp, Lp, H1 floats) are multiples of 16 bytes; g, u, acc_out, y, cost_frames and cost are
+ *     accessed element by element and need their natural alignment only.  Required size: exactly the extent stated, not
+ *     one byte more -- no entry point writes outside it (tests/test_gpu_buffer_contract.py); reads are kept inside by the
+ *     buffer resources of the wave chains, the frame and sample clamps and the bin masks of the other kernels.
  *     Pointers marked HOST are host memory read during the call.
  *   - no allocation happens after vaenmf_plan_create / vaenmf_set_decoder_weights /
  *     vaenmf_bind_batch.
@@ -24,16 +29,45 @@
  * utterances of the bound batch concatenated, NT = total frames)
  *   Fs  = F rounded up to 16        (query VAENMF_Q_FS)    feature row stride
  *   Kp  = 8, 16 or 32 (>= K)        (query VAENMF_Q_KP)    padded NMF rank
- *   X2  float  [NT][Fs]   mixture power spectrogram |X|^2      (mcem.py:47, transposed)
- *   X   float2 [NT][Fs]   mixture STFT, complex64              (mcem.py:46, transposed)
- *   W   float  [U][Fs][Kp] NMF dictionary per utterance        (mcem.py:48)  pad = 0
- *   Ht  float  [NT][Kp]   NMF activations, transposed          (mcem.py:49)  pad = 0
- *   g   float  [NT]       per-frame gain                       (mcem.py:51)
- *   Lp  = 32, or 128 on a wide plan (query VAENMF_Q_LP)    latent row stride; columns L..Lp-1 are zero
- *   Z   float  [NT][Lp]   last draw of the latent variables    (mcem.py:368, transposed)
- *   Zs  float  [NT][Rcap][Lp] posterior samples                (mcem.py:386)
- *   B1  float  [NT][H1]   per-frame first-layer bias b1 + W1[:,L:] y_n  (M2: the label
- *                         part of decoder(cat([Z,y])) folded once, mcem.py:242); NULL = M1
+ *   Lp  = 32, or 128 on a wide plan (query VAENMF_Q_LP)    latent row stride
+ * The padding of a row -- bins F..Fs-1, ranks K..Kp-1, latent columns L..Lp-1, sample rows nsamples..Rcap-1 -- is one of
+ *   must be zero     the caller's duty when it fills the buffer (results are undefined otherwise);
+ *   ignored          any bits, NaN included: no result depends on them;
+ *   written as zero  by every entry point that writes the buffer;
+ *   left alone       neither read into a result nor written.
+ * One buffer needs a fifth word, `must be finite`: zero or any finite value; a NaN or Inf there reaches results.
+ *
+ *   buffer                                                    padding as an input      padding as an output
+ *   X2  float  [NT][Fs]   mixture power spectrogram |X|^2     ignored                  vaenmf_power_spec: |X|^2 of X's padding
+ *                         (mcem.py:47, transposed)                                     (zero, as X's must be zero)
+ *   X   float2 [NT][Fs]   mixture STFT, complex64             must be zero             vaenmf_stft_batch_ex: written as zero
+ *                         (mcem.py:46, transposed)            (the Wiener filters write mask * X there with mask = 0: a
+ *                                                             finite value still gives the zeros promised for S_hat / N_hat,
+ *                                                             a NaN or Inf shows in their padding)
+ *   Vb  float  [NT][Fs]   fixed noise PSD                     ignored                  --
+ *                         (vaenmf_set_noise_psd)
+ *   W   float  [U][Fs][Kp] NMF dictionary per utterance       must be zero             written as zero (vaenmf_init_nmf,
+ *                         (mcem.py:48)                        (bins and ranks)         the M-steps, vaenmf_em_run)
+ *   Ht  float  [NT][Kp]   NMF activations, transposed         must be zero             written as zero (the same)
+ *                         (mcem.py:49)
+ *   g   float  [NT]       per-frame gain (mcem.py:51)         --                       --
+ *   Z   float  [NT][Lp]   last draw of the latent variables   must be zero             written as zero (update_Z != 0),
+ *                         (mcem.py:368, transposed)                                    else left alone like all of Z
+ *   Zs  float  [NT][Rcap][Lp] posterior samples (mcem.py:386) columns L..Lp-1 of the   columns L..Lp-1 of the nsamples rows:
+ *                                                             R rows read: must be     written as zero; rows nsamples..Rcap-1:
+ *                                                             zero; rows R..Rcap-1:    left alone
+ *                                                             ignored
+ *   B1  float  [NT][H1]   per-frame first-layer bias b1 + W1[:,L:] y_n  (M2: the label part of decoder(cat([Z,y]))
+ *                         folded once, mcem.py:242); NULL = M1                          --
+ *   eps float  [S][NT][Lp] replay draws (vaenmf_rng)          wide plan: ignored.      vaenmf_rng_fill: finite draws (a narrow
+ *                                                             Narrow plan with L = 16: plan fills all 32 columns)
+ *                                                             must be finite (the wave chains multiply columns 16..31
+ *                                                             by a zero step instead of masking them)
+ *   u, acc_out float [S][NT]; cost_frames double [NT]; cost double [U][niter]           no padding
+ *   S_hat, N_hat float2 [NT][Fs]; WFs, WFn float [NT][Fs];    --                       written as zero
+ *   Vs_out of vaenmf_decode float [NT][R][Fs]
+ *   Vs_out of vaenmf_sample_store_gather [NT][nsamples][Fs]   --                       unspecified (inside the buffer)
+ * Rows: no entry point touches a row >= NT (>= U for W) of any buffer, whatever the tiling of the batch leaves idle.
  *
  * Supported value range
  *   The chain's energy takes one logarithm and one reciprocal for two bins, log(Vx0 Vx1) and
@@ -156,8 +190,8 @@ int vaenmf_set_noise_psd(vaenmf_plan* p, const float* Vb);
  * update_Z != 0: Z is overwritten with the last draw, as E_step does (mcem.py:466);
  * update_Z == 0: Z is only read, as compute_WF does (mcem.py:477-478).  acc_out (DEV
  * [S][NT], may be NULL) receives the log-acceptance of every step (mcem.py:415-417).
- * Zs may be NULL where the wave-private chain kernels run (vaenmf_wchain_addressable; every shape but F > 528 and bf16x3 with
- * F > 272): the samples are then not recorded -- with the sample-variance store on nothing reads them (vaenmf_em_run does
+ * Zs may be NULL on a wide plan and where the wave-private chain kernels run (vaenmf_wchain_addressable; every narrow shape
+ * but F > 528 and bf16x3 with F > 272): the samples are then not recorded -- with the sample-variance store on nothing reads them (vaenmf_em_run does
  * this for its E-steps). */
 int vaenmf_mh_chain(vaenmf_plan* p, const float* X2, const float* W, const float* Ht, const float* g,
                     float* Z, int32_t update_Z, const float* B1, float* Zs, int32_t Rcap,
