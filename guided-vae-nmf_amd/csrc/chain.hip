@@ -109,6 +109,102 @@ __device__ __forceinline__ f32x4 tanh4(const f32x4 a) {
   return f32x4{h0[0], h0[1], h1[0], h1[1]};
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// What wchain_kernel and wchain4_kernel share as functions: the buffer resources, the per-tile constants, the frame of a
+// lane, the load of its latent state and the final write of Z.  Each kernel keeps its weights, its tile ownership, its
+// layer-1 bias rows and its energy evaluation.  The byte offsets, the noise streams and the MH step are still written
+// out in both kernels; DESIGN.md 3.1 has the scratch figures that kept them there.
+// ---------------------------------------------------------------------------------------------------------------
+// Every per-frame address of the chain is a buffer resource (SGPRs) + one 32-bit byte offset per lane: no 64-bit
+// address pairs live across the chain (spilled, they were reloaded from scratch before each store, and a scratch
+// reload waits for every store in flight: vmcnt counts in order).  Lanes without a frame get an offset behind
+// the buffer's size (WC_OOB): the hardware drops their stores and returns 0 for their loads, no predicate needed.
+struct WcRes {
+  __amdgpu_buffer_rsrc_t vrs, zs_rs, src_rs, acc_rs, eps_rs, x2in_rs, vbin_rs, w_rs, h_rs, z_rs, b1in_rs, u_rs;
+};
+template <bool STORE, bool M2>
+__device__ __forceinline__ WcRes wc_resources(const WcArgs& a) {
+  const int S = a.nsamples + a.burnin;
+  WcRes r;
+  r.vrs = __builtin_amdgcn_make_buffer_rsrc(a.VsS, 0, STORE ? (int)a.VsS_bytes : 0, 0x00020000);
+  r.zs_rs = __builtin_amdgcn_make_buffer_rsrc(a.Zs, 0, a.Zs ? (int)((unsigned)a.NT * (unsigned)a.Rcap * LAT * 4u) : 0, 0x00020000);   // (no Zs: the sample stores fall outside the resource and are dropped)
+  r.src_rs = __builtin_amdgcn_make_buffer_rsrc(a.src, 0, STORE ? (int)((unsigned)a.NT * (unsigned)a.Rs * 4u) : 0, 0x00020000);
+  r.acc_rs = __builtin_amdgcn_make_buffer_rsrc(a.acc_out, 0, a.acc_out ? (int)((unsigned)a.NT * (unsigned)S * 4u) : 0, 0x00020000);
+  r.eps_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.eps), 0, a.eps ? (int)((unsigned)a.NT * (unsigned)S * LAT * 4u) : 0, 0x00020000);
+  r.x2in_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.X2), 0, (int)((unsigned)a.NT * (unsigned)a.Fs * 4u), 0x00020000);
+  r.vbin_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.Vb), 0, a.Vb ? (int)((unsigned)a.NT * (unsigned)a.Fs * 4u) : 0, 0x00020000);
+  r.w_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.W), 0, a.W ? (int)((unsigned)a.n_utts * (unsigned)a.Fs * (unsigned)a.Kp * 4u) : 0, 0x00020000);
+  r.h_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.Ht), 0, a.Ht ? (int)((unsigned)a.NT * (unsigned)a.Kp * 4u) : 0, 0x00020000);
+  r.z_rs = __builtin_amdgcn_make_buffer_rsrc(a.Z, 0, (int)((unsigned)a.NT * LAT * 4u), 0x00020000);
+  r.b1in_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.B1), 0, M2 ? (int)((unsigned)a.NT * HID * 4u) : 0, 0x00020000);
+  r.u_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.u), 0, a.u ? (int)((unsigned)a.NT * (unsigned)S * 4u) : 0, 0x00020000);
+  return r;
+}
+
+// Per-(bin, frame) constants of the bin tile whose first bin in this lane is f0, in accumulator layout: X2 and Vb = W H
+// (mcem.py:81-82) or the given noise PSD.  Padding bins: X2 = 0, Vb = 1 and (b3 = -200, W3 = 0) Vs = 0, so their term
+// is exactly 0.  rowF / uF: first element of the frame's row / of the utterance's block of W rows.
+// Through buffer resources: a tile's address is the resource (SGPRs) + one per-lane byte offset + a scalar or
+// immediate tile offset.  With 64-bit pointers the compiler kept an address pair per (tile, bin) alive and spilled
+// them -- the only scratch of the kernel, and a kernel with scratch pays a scratch-memory set-up per dispatch.
+__device__ __forceinline__ void wc_tile_consts(const WcArgs& a, const WcRes& R, unsigned rowF, unsigned uF, int nrow, int f0, f32x4& x2, f32x4& vb) {
+  f32x4 xv = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(R.x2in_rs, (rowF + (unsigned)f0) * 4u, 0, 0));
+  f32x4 v = {0, 0, 0, 0};
+  if (a.Vb) {
+    v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(R.vbin_rs, (rowF + (unsigned)f0) * 4u, 0, 0));
+  } else {
+    for (int k = 0; k < a.Kp; k += 4) {              // (once per launch: a plain loop, operands from L1/L2)
+      const f32x4 h4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(R.h_rs, ((unsigned)nrow * (unsigned)a.Kp + (unsigned)k) * 4u, 0, 0));
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const f32x4 w4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(R.w_rs, ((uF + (unsigned)(f0 + j)) * (unsigned)a.Kp + (unsigned)k) * 4u, 0, 0));
+        v[j] += w4[0] * h4[0] + w4[1] * h4[1] + w4[2] * h4[2] + w4[3] * h4[3];
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (f0 + j >= a.F) { xv[j] = 0.f; v[j] = 1.f; }
+  x2 = xv;
+  vb = v;
+}
+
+// The frame of lane column c in wave tile wt.  writer: this wavefront writes the chain's bookkeeping (samples, slot map,
+// acceptances, Z) -- every wavefront of wchain_kernel, wavefront 0 of wchain4_kernel; the sample-variance rows are
+// written by every wavefront that computes a part of them.
+struct WcFrame {
+  int utt, nrow;
+  bool fvalid;               // the lane has a frame of its own
+  bool keeps;                // ... and writes the bookkeeping for it
+};
+__device__ __forceinline__ WcFrame wc_frame(const WcArgs& a, int wt, int c, bool writer) {
+  WcFrame fr;
+  const int n0 = a.wt_n0[wt], cnt = a.wt_cnt[wt];
+  fr.utt = a.wt_utt[wt];
+  fr.fvalid = c < cnt;
+  fr.keeps = fr.fvalid && writer;
+  fr.nrow = n0 + (fr.fvalid ? c : cnt - 1);               // idle lanes shadow the last frame (no stores)
+  return fr;
+}
+// Current latent state of the lane's frame, fragment order: latents 4q..4q+3 and 16+4q..16+4q+3 of frame c
+__device__ __forceinline__ void wc_load_z(const WcRes& R, const WcFrame& fr, int q, float (&z)[8]) {
+  // (buffer-addressed like everything else per frame: a 64-bit address pair here was loop-invariant in its lane part,
+  //  hoisted out of the wave-tile loop and spilled -- the kernel's only scratch)
+  const unsigned zo = ((unsigned)fr.nrow * LAT + 4u * (unsigned)q) * 4u;
+  const f32x4 lo = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(R.z_rs, zo, 0, 0));
+  const f32x4 hi = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(R.z_rs, zo + 64u, 0, 0));
+#pragma unroll
+  for (int t = 0; t < 4; ++t) { z[t] = lo[t]; z[4 + t] = hi[t]; }
+}
+// self.Z = last draw (mcem.py:466); idle lanes: offset behind the buffer
+__device__ __forceinline__ void wc_store_z(const WcArgs& a, const WcRes& R, const WcFrame& fr, unsigned rp_off, const float (&z)[8]) {
+  if (a.update_Z) {
+    const unsigned zo = fr.keeps ? rp_off : WC_OOB;
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{z[0], z[1], z[2], z[3]}), R.z_rs, zo, 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{z[4], z[5], z[6], z[7]}), R.z_rs, zo + 64u, 0, 0);
+  }
+}
+
 // MAXT : compile-time bound of the bin tiles; EXACT: NT3 == MAXT (no per-tile checks)
 // LOL  : the lo fragments of W3 are in LDS too (bf16x3 mode, small F); otherwise they stream from L2
 // HIALL: every hi fragment of W3 is in LDS
@@ -165,25 +261,11 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
   const float* b3l = reinterpret_cast<const float*>(smem + L::B3);
   const char* w3lo_lds = smem + L::W3 + (size_t)n_hi * NK_H * 1024;
   const char* w3g = reinterpret_cast<const char*>(a.w3f);
-  const int S = a.nsamples + a.burnin;
-  // first of this lane's 4 consecutive bins in tile t
   const int Tm = EXACT ? ((MAXT - 1) & ~1) : a.Tm;
-  auto bin0 = [&](int t) { return (!SPLIT && t < Tm) ? 32 * (t >> 1) + 8 * q + 4 * (t & 1) : 16 * t + 4 * q; };
   auto tile_on = [&](int t) { return EXACT || t < NT3; };
   auto tile_on3 = [&](int n, int t) { return n != MAXT || EXACT || t < NT3; };      // (hidden layers: every tile)
 
-  __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(a.VsS, 0, STORE ? (int)a.VsS_bytes : 0, 0x00020000);
-  __amdgpu_buffer_rsrc_t zs_rs = __builtin_amdgcn_make_buffer_rsrc(a.Zs, 0, a.Zs ? (int)((unsigned)a.NT * (unsigned)a.Rcap * LAT * 4u) : 0, 0x00020000);   // (no Zs: the sample stores fall outside the resource and are dropped)
-  __amdgpu_buffer_rsrc_t src_rs = __builtin_amdgcn_make_buffer_rsrc(a.src, 0, STORE ? (int)((unsigned)a.NT * (unsigned)a.Rs * 4u) : 0, 0x00020000);
-  __amdgpu_buffer_rsrc_t acc_rs = __builtin_amdgcn_make_buffer_rsrc(a.acc_out, 0, a.acc_out ? (int)((unsigned)a.NT * (unsigned)S * 4u) : 0, 0x00020000);
-  __amdgpu_buffer_rsrc_t eps_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.eps), 0, a.eps ? (int)((unsigned)a.NT * (unsigned)S * LAT * 4u) : 0, 0x00020000);
-  __amdgpu_buffer_rsrc_t x2in_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.X2), 0, (int)((unsigned)a.NT * (unsigned)a.Fs * 4u), 0x00020000);
-  __amdgpu_buffer_rsrc_t vbin_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.Vb), 0, a.Vb ? (int)((unsigned)a.NT * (unsigned)a.Fs * 4u) : 0, 0x00020000);
-  __amdgpu_buffer_rsrc_t w_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.W), 0, a.W ? (int)((unsigned)a.n_utts * (unsigned)a.Fs * (unsigned)a.Kp * 4u) : 0, 0x00020000);
-  __amdgpu_buffer_rsrc_t h_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.Ht), 0, a.Ht ? (int)((unsigned)a.NT * (unsigned)a.Kp * 4u) : 0, 0x00020000);
-  __amdgpu_buffer_rsrc_t z_rs = __builtin_amdgcn_make_buffer_rsrc(a.Z, 0, (int)((unsigned)a.NT * LAT * 4u), 0x00020000);
-  __amdgpu_buffer_rsrc_t b1in_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.B1), 0, M2 ? (int)((unsigned)a.NT * HID * 4u) : 0, 0x00020000);
-  __amdgpu_buffer_rsrc_t u_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.u), 0, a.u ? (int)((unsigned)a.NT * (unsigned)S * 4u) : 0, 0x00020000);
+  const WcRes R = wc_resources<STORE, M2>(a);
 
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   // wave tile of (workgroup b, wavefront w, round i): (i NWAVES + w) gridDim + b -- a batch with fewer tiles than wavefront
@@ -191,21 +273,17 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
   // workgroups, and a lone wavefront has its SIMD's issue slots to itself (one 4 s utterance through the drop-in classes:
   // 80.5 -> 69.0 ms; the 64-utterance batch: unchanged)
   for (int wt = wave * (int)gridDim.x + (int)blockIdx.x; wt < a.n_wtiles; wt += (int)gridDim.x * NWAVES) {
-    const int utt = a.wt_utt[wt], n0 = a.wt_n0[wt], cnt = a.wt_cnt[wt];
-    const bool fvalid = c < cnt;
-    const int nrow = n0 + (fvalid ? c : cnt - 1);          // idle lanes shadow the last frame (no stores)
+    const WcFrame fr = wc_frame(a, wt, c, true);
+    const int nrow = fr.nrow;
     const float gn = a.g[nrow];
-    // ---- per-(bin, frame) constants in accumulator layout: X2 and Vb = W H (mcem.py:81-82) or the given noise PSD.
-    // Padding bins: X2 = 0, Vb = 1 and (b3 = -200, W3 = 0) Vs = 0, so their term is exactly 0.
+    // ---- per-(bin, frame) constants of every bin tile, accumulator layout (wc_tile_consts)
     f32x4 x2[MAXT], vb[MAXT];
     {
-      // Through buffer resources: a tile's address is the resource (SGPRs) + one per-lane byte offset + a scalar or
-      // immediate tile offset.  With 64-bit pointers the compiler kept an address pair per (tile, bin) alive and spilled
-      // them -- the only scratch of the kernel, and a kernel with scratch pays a scratch-memory set-up per dispatch.
       const unsigned rowF = (unsigned)nrow * (unsigned)a.Fs;                     // first element of the frame's row
-      const unsigned uF = (unsigned)utt * (unsigned)a.Fs;
+      const unsigned uF = (unsigned)fr.utt * (unsigned)a.Fs;
       int qo = q;                                            // (opaque: the per-tile bin numbers are recomputed here, once per
       asm volatile("" : "+v"(qo));                           //  wave tile, instead of being hoisted out of the loop and spilled)
+      // first of this lane's 4 consecutive bins in tile t
       auto bin0o = [&](int t) { return (!SPLIT && t < Tm) ? 32 * (t >> 1) + 8 * qo + 4 * (t & 1) : 16 * t + 4 * qo; };
 #pragma unroll
       for (int t = 0; t < MAXT; ++t) {
@@ -213,25 +291,7 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
         vb[t] = f32x4{1, 1, 1, 1};
         if (tile_on(t)) {
           const int f0 = bin0o(t);
-          f32x4 xv = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(x2in_rs, (rowF + (unsigned)f0) * 4u, 0, 0));
-          f32x4 v = {0, 0, 0, 0};
-          if (a.Vb) {
-            v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(vbin_rs, (rowF + (unsigned)f0) * 4u, 0, 0));
-          } else {
-            for (int k = 0; k < a.Kp; k += 4) {              // (once per launch: a plain loop, operands from L1/L2)
-              const f32x4 h4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(h_rs, ((unsigned)nrow * (unsigned)a.Kp + (unsigned)k) * 4u, 0, 0));
-#pragma unroll
-              for (int j = 0; j < 4; ++j) {
-                const f32x4 w4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(w_rs, ((uF + (unsigned)(f0 + j)) * (unsigned)a.Kp + (unsigned)k) * 4u, 0, 0));
-                v[j] += w4[0] * h4[0] + w4[1] * h4[1] + w4[2] * h4[2] + w4[3] * h4[3];
-              }
-            }
-          }
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (f0 + j >= a.F) { xv[j] = 0.f; v[j] = 1.f; }
-          x2[t] = xv;
-          vb[t] = v;
+          wc_tile_consts(a, R, rowF, uF, nrow, f0, x2[t], vb[t]);
         }
       }
     }
@@ -241,43 +301,30 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
     if (M2) {
 #pragma unroll
       for (int t = 0; t < NT_H; ++t) {
-        const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(b1in_rs, ((unsigned)nrow * HID + 4u * (unsigned)q) * 4u + 64u * (unsigned)t, 0, 0));
+        const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(R.b1in_rs, ((unsigned)nrow * HID + 4u * (unsigned)q) * 4u + 64u * (unsigned)t, 0, 0));
         if (B1L) *reinterpret_cast<u32x2*>(b1stash + t * 512) = u32x2{pk2(v[0], v[1]), pk2(v[2], v[3])};
         else b1r[(M2 && !B1L) ? t : 0] = v;
       }
     }
-    // ---- current latent state, fragment order: latents 4q..4q+3 and 16+4q..16+4q+3 of frame c
     float z[8];
-    {
-      // (buffer-addressed like everything else per frame: a 64-bit address pair here was loop-invariant in its lane part,
-      //  hoisted out of the wave-tile loop and spilled -- the kernel's only scratch)
-      const unsigned zo = ((unsigned)nrow * LAT + 4u * (unsigned)q) * 4u;
-      const f32x4 lo = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(z_rs, zo, 0, 0));
-      const f32x4 hi = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(z_rs, zo + 64u, 0, 0));
-#pragma unroll
-      for (int t = 0; t < 4; ++t) { z[t] = lo[t]; z[4 + t] = hi[t]; }
-    }
+    wc_load_z(R, fr, q, z);
     // ---- sample-variance store: slot r of the frame holds the variances of the proposal of post-burn-in step r,
     // slot R the state the chain is in when the burn-in ends; src[r][frame] names the slot of the state after
-    // step r (mcem.py:429-437).
-    // Every per-frame address of the loop is a buffer resource (SGPRs) + one 32-bit byte offset per lane: no 64-bit
-    // address pairs live across the chain (spilled, they were reloaded from scratch before each store, and a scratch
-    // reload waits for every store in flight: vmcnt counts in order).  Lanes without a frame get an offset behind
-    // the buffer's size: the hardware drops their stores and returns 0 for their loads, no predicate needed.
-    const unsigned fbase = STORE ? (fvalid ? (unsigned)nrow * (unsigned)(a.Rs * a.Fs) * (unsigned)sizeof(store_t) : WC_OOB) : 0u;
-    const unsigned zs_off = fvalid ? ((unsigned)nrow * (unsigned)a.Rcap * LAT + 4u * q) * 4u : WC_OOB;      // Zs[nrow][r][4q..]
-    const unsigned fr_off = (fvalid && q == 0) ? (unsigned)nrow * 4u : WC_OOB;                                  // [step][nrow] tables
+    // step r (mcem.py:429-437; the slot of a pass: vn_chain_pass, common.h)
+    const unsigned fbase = STORE ? (fr.fvalid ? (unsigned)nrow * (unsigned)(a.Rs * a.Fs) * (unsigned)sizeof(store_t) : WC_OOB) : 0u;
+    const unsigned zs_off = fr.fvalid ? ((unsigned)nrow * (unsigned)a.Rcap * LAT + 4u * q) * 4u : WC_OOB;      // Zs[nrow][r][4q..]
+    const unsigned fr_off = (fr.fvalid && q == 0) ? (unsigned)nrow * 4u : WC_OOB;                                  // [step][nrow] tables
     const unsigned rp_off = ((unsigned)nrow * LAT + 4u * q) * 4u;                                               // eps[step][nrow][4q..]
     int cur_src = a.nsamples;
     // ---- noise streams: this lane draws latents 4q..4q+3 (stream q) and 16+4q.. (stream 4+q) of its frame;
     // the streams are keyed by (utterance seed, frame inside the utterance, latent quad, chain call)
     Xs128 st0, st1;
     if (a.rng_mode == VAENMF_RNG_DEVICE) {
-      const uint32_t floc = (uint32_t)(nrow - a.frame_off[utt]);
+      const uint32_t floc = (uint32_t)(nrow - a.frame_off[fr.utt]);
       int qs = q;                                          // (opaque: the key words are built here, once per wave tile, not hoisted and spilled)
       asm volatile("" : "+v"(qs));
-      st0 = xs_seed(a.utt_seed[utt], floc, (uint32_t)qs, a.call);
-      st1 = xs_seed(a.utt_seed[utt], floc, (uint32_t)(4 + qs), a.call);
+      st0 = xs_seed(a.utt_seed[fr.utt], floc, (uint32_t)qs, a.call);
+      st1 = xs_seed(a.utt_seed[fr.utt], floc, (uint32_t)(4 + qs), a.call);
     }
 
     // E(z) = sum_f [log Vx + X2 / Vx] of this lane's frame (all lanes of the frame get the sum).  fp64 across
@@ -457,14 +504,14 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
                   }
                   if (DOST) {
                     if (SPLIT) {
-                      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, ev), vrs, voff + 16u * q + 64u * t, 0, WC_ST_AUX);
+                      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, ev), R.vrs, voff + 16u * q + 64u * t, 0, WC_ST_AUX);
                     } else {
                       const unsigned p0 = pk2(ev[0], ev[1]), p1 = pk2(ev[2], ev[3]);
                       if (t < Tm) {
                         if ((t & 1) == 0) { pk_even0 = p0; pk_even1 = p1; }
-                        else __builtin_amdgcn_raw_buffer_store_b128(u32x4{pk_even0, pk_even1, p0, p1}, vrs, voff + 16u * q + 64u * (t >> 1), 0, WC_ST_AUX);
+                        else __builtin_amdgcn_raw_buffer_store_b128(u32x4{pk_even0, pk_even1, p0, p1}, R.vrs, voff + 16u * q + 64u * (t >> 1), 0, WC_ST_AUX);
                       } else {
-                        __builtin_amdgcn_raw_buffer_store_b64(u32x2{p0, p1}, vrs, voff + 8u * q + 32u * t, 0, WC_ST_AUX);
+                        __builtin_amdgcn_raw_buffer_store_b64(u32x2{p0, p1}, R.vrs, voff + 8u * q + 32u * t, 0, WC_ST_AUX);
                       }
                     }
                   }
@@ -479,18 +526,16 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
     };
 
     double Ecur = 0.0;
-    // it = -1 evaluates the initial state (mcem.py:392-400); it >= 0 are the MH steps.  With the store on and a
-    // burn-in, one more pass after the burn-in re-evaluates the state the chain is in (nothing drawn, nothing
-    // decided) so that its variances are on record in slot R.
-    const bool reeval = STORE && a.burnin > 0;
+    // The passes of vn_chain_pass (common.h): the initial state, the MH steps, with the store on the re-evaluation.
     // retire the prologue's loads here: a counted vmcnt wait for them placed inside the loop would, on every later
     // step, wait for the previous step's stores instead (vmcnt counts loads and stores in order)
     __builtin_amdgcn_s_waitcnt(0x0F70);                 // vmcnt(0), gfx9 encoding
-    for (int it = -1; it < S + (reeval ? 1 : 0); ++it) {
+    const int n_it = vn_chain_passes<STORE>(a.nsamples, a.burnin);
+    for (int it = -1; it < n_it; ++it) {
       asm volatile("" ::: "memory");            // the LDS-resident weights are re-read every step (no hoisting into registers)
-      const bool re = reeval && it == a.burnin;
-      const int m = (reeval && it > a.burnin) ? it - 1 : it;
-      const bool step = m >= 0 && !re;
+      const VnChainPass ps = vn_chain_pass<STORE>(it, a.nsamples, a.burnin);
+      const bool re = ps.re, step = ps.step;
+      const int m = ps.m, slot = ps.slot;
       // ---- noise of this step and the proposal Z' = Z + sqrt(var) randn (mcem.py:407)
       float zp[8];
       float lu = 0.f;                                   // log U(0,1) of the frame (mcem.py:420), lanes q = 0
@@ -507,9 +552,9 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
           lu = q == 0 ? fast_log(uu) : 0.f;
         } else {
           const unsigned so = (unsigned)m * (unsigned)a.NT;      // step offset in rows
-          const f32x4 e0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(eps_rs, rp_off + so * (LAT * 4u), 0, 0));
-          const f32x4 e1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(eps_rs, rp_off + so * (LAT * 4u) + 64u, 0, 0));
-          const float uu = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(u_rs, (unsigned)nrow * 4u + so * 4u, 0, 0));
+          const f32x4 e0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(R.eps_rs, rp_off + so * (LAT * 4u), 0, 0));
+          const f32x4 e1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(R.eps_rs, rp_off + so * (LAT * 4u) + 64u, 0, 0));
+          const float uu = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(R.u_rs, (unsigned)nrow * 4u + so * 4u, 0, 0));
 #pragma unroll
           for (int t = 0; t < 4; ++t) { zp[t] = z[t] + a.sd * e0[t]; zp[4 + t] = z[4 + t] + a.sd_hi * e1[t]; }
           lu = q == 0 ? fast_log(uu) : 0.f;
@@ -522,7 +567,6 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
         for (int t = 0; t < 8; ++t) zp[t] = z[t];
       }
       WC_STAMP(0);
-      const int slot = !STORE ? -1 : (re ? a.nsamples : (m >= a.burnin ? m - a.burnin : ((m < 0 && a.burnin == 0) ? a.nsamples : -1)));
       double Ep;
       if (STORE && slot >= 0) Ep = energy(zp, slot, std::true_type{});
       else Ep = energy(zp, slot, std::false_type{});
@@ -536,7 +580,7 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
       WC_STAMP(6);
       const float accp = (float)(Ecur - Ep) + 0.5f * pr;
       const bool ok = m < 0 || lu < accp;               // mcem.py:420
-      if (a.acc_out && m >= 0) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, accp), acc_rs, fr_off + (unsigned)m * (unsigned)a.NT * 4u, 0, 0);
+      if (a.acc_out && m >= 0) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, accp), R.acc_rs, fr_off + (unsigned)m * (unsigned)a.NT * 4u, 0, 0);
       // mcem.py:429-433, as selects (no divergent branch in the loop)
 #pragma unroll
       for (int j = 0; j < 8; ++j) z[j] = ok ? zp[j] : z[j];
@@ -546,20 +590,16 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
         const unsigned r = (unsigned)(m - a.burnin);
         if (STORE) {
           cur_src = ok ? (int)r : cur_src;
-          __builtin_amdgcn_raw_buffer_store_b32((unsigned)cur_src, src_rs, fr_off + r * (unsigned)a.NT * 4u, 0, 0);
+          __builtin_amdgcn_raw_buffer_store_b32((unsigned)cur_src, R.src_rs, fr_off + r * (unsigned)a.NT * 4u, 0, 0);
         }
         const unsigned zo = zs_off + r * (LAT * 4u);
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{z[0], z[1], z[2], z[3]}), zs_rs, zo, 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{z[4], z[5], z[6], z[7]}), zs_rs, zo + 64u, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{z[0], z[1], z[2], z[3]}), R.zs_rs, zo, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{z[4], z[5], z[6], z[7]}), R.zs_rs, zo + 64u, 0, 0);
       }
       WC_STAMP(4);
     }
     WC_STAMP_FLUSH;
-    if (a.update_Z) {                                   // self.Z = last draw (mcem.py:466); idle lanes: offset behind the buffer
-      const unsigned zo = fvalid ? rp_off : WC_OOB;
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{z[0], z[1], z[2], z[3]}), z_rs, zo, 0, 0);
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{z[4], z[5], z[6], z[7]}), z_rs, zo + 64u, 0, 0);
-    }
+    wc_store_z(a, R, fr, rp_off, z);
   }
 }
 
@@ -590,7 +630,6 @@ __global__ __launch_bounds__(256, 1) void wchain4_kernel(const WcArgs a) {
 
   const int lane = threadIdx.x & 63, q = lane >> 4, c = lane & 15;
   const unsigned l16 = (unsigned)lane * 16u;
-  const int S = a.nsamples + a.burnin;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   // owned bin tiles: the pairs wave, wave + 4, ... (tiles 2p, 2p+1); wavefront 0 also tile MAXT-1
   auto tile_of = [&](int i) { return i < 2 * PPW ? 2 * (wave + 4 * (i >> 1)) + (i & 1) : MAXT - 1; };
@@ -623,27 +662,15 @@ __global__ __launch_bounds__(256, 1) void wchain4_kernel(const WcArgs a) {
     }
   }
 
-  __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(a.VsS, 0, STORE ? (int)a.VsS_bytes : 0, 0x00020000);
-  __amdgpu_buffer_rsrc_t zs_rs = __builtin_amdgcn_make_buffer_rsrc(a.Zs, 0, a.Zs ? (int)((unsigned)a.NT * (unsigned)a.Rcap * LAT * 4u) : 0, 0x00020000);   // (no Zs: the sample stores fall outside the resource and are dropped)
-  __amdgpu_buffer_rsrc_t src_rs = __builtin_amdgcn_make_buffer_rsrc(a.src, 0, STORE ? (int)((unsigned)a.NT * (unsigned)a.Rs * 4u) : 0, 0x00020000);
-  __amdgpu_buffer_rsrc_t acc_rs = __builtin_amdgcn_make_buffer_rsrc(a.acc_out, 0, a.acc_out ? (int)((unsigned)a.NT * (unsigned)S * 4u) : 0, 0x00020000);
-  __amdgpu_buffer_rsrc_t eps_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.eps), 0, a.eps ? (int)((unsigned)a.NT * (unsigned)S * LAT * 4u) : 0, 0x00020000);
-  __amdgpu_buffer_rsrc_t x2in_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.X2), 0, (int)((unsigned)a.NT * (unsigned)a.Fs * 4u), 0x00020000);
-  __amdgpu_buffer_rsrc_t vbin_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.Vb), 0, a.Vb ? (int)((unsigned)a.NT * (unsigned)a.Fs * 4u) : 0, 0x00020000);
-  __amdgpu_buffer_rsrc_t w_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.W), 0, a.W ? (int)((unsigned)a.n_utts * (unsigned)a.Fs * (unsigned)a.Kp * 4u) : 0, 0x00020000);
-  __amdgpu_buffer_rsrc_t h_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.Ht), 0, a.Ht ? (int)((unsigned)a.NT * (unsigned)a.Kp * 4u) : 0, 0x00020000);
-  __amdgpu_buffer_rsrc_t z_rs = __builtin_amdgcn_make_buffer_rsrc(a.Z, 0, (int)((unsigned)a.NT * LAT * 4u), 0x00020000);
-  __amdgpu_buffer_rsrc_t b1in_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.B1), 0, M2 ? (int)((unsigned)a.NT * HID * 4u) : 0, 0x00020000);
-  __amdgpu_buffer_rsrc_t u_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.u), 0, a.u ? (int)((unsigned)a.NT * (unsigned)S * 4u) : 0, 0x00020000);
+  const WcRes R = wc_resources<STORE, M2>(a);
 
   for (int wt = blockIdx.x; wt < a.n_wtiles; wt += (int)gridDim.x) {
-    const int utt = a.wt_utt[wt], n0 = a.wt_n0[wt], cnt = a.wt_cnt[wt];
-    const bool fvalid = c < cnt;
-    const int nrow = n0 + (fvalid ? c : cnt - 1);
+    const WcFrame fr = wc_frame(a, wt, c, wave == 0);
+    const int nrow = fr.nrow;
     const float gn = a.g[nrow];
-    f32x4 x2[NOWN], vb[NOWN];
+    f32x4 x2[NOWN], vb[NOWN];                              // the constants of this wavefront's bin tiles (wc_tile_consts)
     {
-      const unsigned rowF = (unsigned)nrow * (unsigned)a.Fs, uF = (unsigned)utt * (unsigned)a.Fs;
+      const unsigned rowF = (unsigned)nrow * (unsigned)a.Fs, uF = (unsigned)fr.utt * (unsigned)a.Fs;
 #pragma unroll
       for (int i = 0; i < NOWN; ++i) {
         x2[i] = f32x4{0, 0, 0, 0};
@@ -651,25 +678,7 @@ __global__ __launch_bounds__(256, 1) void wchain4_kernel(const WcArgs a) {
         if (own(i)) {
           const int t = tile_of(i);
           const int f0 = t < MAXT - 1 ? 32 * (t >> 1) + 8 * q + 4 * (t & 1) : 16 * t + 4 * q;      // the chain's bin order (see the file header)
-          f32x4 xv = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(x2in_rs, (rowF + (unsigned)f0) * 4u, 0, 0));
-          f32x4 v = {0, 0, 0, 0};
-          if (a.Vb) {
-            v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(vbin_rs, (rowF + (unsigned)f0) * 4u, 0, 0));
-          } else {
-            for (int k = 0; k < a.Kp; k += 4) {          // the same order of operations as wchain_kernel's prologue
-              const f32x4 h4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(h_rs, ((unsigned)nrow * (unsigned)a.Kp + (unsigned)k) * 4u, 0, 0));
-#pragma unroll
-              for (int j = 0; j < 4; ++j) {
-                const f32x4 w4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(w_rs, ((uF + (unsigned)(f0 + j)) * (unsigned)a.Kp + (unsigned)k) * 4u, 0, 0));
-                v[j] += w4[0] * h4[0] + w4[1] * h4[1] + w4[2] * h4[2] + w4[3] * h4[3];
-              }
-            }
-          }
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (f0 + j >= a.F) { xv[j] = 0.f; v[j] = 1.f; }
-          x2[i] = xv;
-          vb[i] = v;
+          wc_tile_consts(a, R, rowF, uF, nrow, f0, x2[i], vb[i]);
         }
       }
     }
@@ -678,7 +687,7 @@ __global__ __launch_bounds__(256, 1) void wchain4_kernel(const WcArgs a) {
     if (M2) {
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(b1in_rs, ((unsigned)nrow * HID + 4u * (unsigned)q) * 4u + 64u * (unsigned)(2 * wave + i), 0, 0));
+        const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(R.b1in_rs, ((unsigned)nrow * HID + 4u * (unsigned)q) * 4u + 64u * (unsigned)(2 * wave + i), 0, 0));
         if (B1BF) {      // (rounded to bf16 like the rows wchain_kernel parks in LDS at 8 wavefronts: the same bits in both kernels)
           const unsigned w0 = pk2(v[0], v[1]), w1 = pk2(v[2], v[3]);
           b1r[i] = f32x4{bf_lo(w0), bf_hi(w0), bf_lo(w1), bf_hi(w1)};
@@ -686,25 +695,18 @@ __global__ __launch_bounds__(256, 1) void wchain4_kernel(const WcArgs a) {
       }
     }
     float z[8];
-    {
-      const unsigned zo = ((unsigned)nrow * LAT + 4u * (unsigned)q) * 4u;
-      const f32x4 lo = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(z_rs, zo, 0, 0));
-      const f32x4 hi = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(z_rs, zo + 64u, 0, 0));
-#pragma unroll
-      for (int t = 0; t < 4; ++t) { z[t] = lo[t]; z[4 + t] = hi[t]; }
-    }
+    wc_load_z(R, fr, q, z);
     // rows: every wavefront writes its own tiles' part; samples, slot map, acceptances and Z: wavefront 0 alone
-    const bool w0 = wave == 0;
-    const unsigned fbase = STORE ? (fvalid ? (unsigned)nrow * (unsigned)(a.Rs * a.Fs) * 2u : WC_OOB) : 0u;
-    const unsigned zs_off = (fvalid && w0) ? ((unsigned)nrow * (unsigned)a.Rcap * LAT + 4u * q) * 4u : WC_OOB;
-    const unsigned fr_off = (fvalid && w0 && q == 0) ? (unsigned)nrow * 4u : WC_OOB;
+    const unsigned fbase = STORE ? (fr.fvalid ? (unsigned)nrow * (unsigned)(a.Rs * a.Fs) * 2u : WC_OOB) : 0u;
+    const unsigned zs_off = fr.keeps ? ((unsigned)nrow * (unsigned)a.Rcap * LAT + 4u * q) * 4u : WC_OOB;
+    const unsigned fr_off = (fr.keeps && q == 0) ? (unsigned)nrow * 4u : WC_OOB;
     const unsigned rp_off = ((unsigned)nrow * LAT + 4u * q) * 4u;
     int cur_src = a.nsamples;
     Xs128 st0, st1;
     if (a.rng_mode == VAENMF_RNG_DEVICE) {
-      const uint32_t floc = (uint32_t)(nrow - a.frame_off[utt]);
-      st0 = xs_seed(a.utt_seed[utt], floc, (uint32_t)q, a.call);
-      st1 = xs_seed(a.utt_seed[utt], floc, (uint32_t)(4 + q), a.call);
+      const uint32_t floc = (uint32_t)(nrow - a.frame_off[fr.utt]);
+      st0 = xs_seed(a.utt_seed[fr.utt], floc, (uint32_t)q, a.call);
+      st1 = xs_seed(a.utt_seed[fr.utt], floc, (uint32_t)(4 + q), a.call);
     }
 
     auto energy = [&](const float (&zz)[8], int slot, auto dost) -> double {
@@ -775,9 +777,9 @@ __global__ __launch_bounds__(256, 1) void wchain4_kernel(const WcArgs a) {
           const unsigned t = (unsigned)tile_of(i);
           if (i < 2 * PPW) {
             if ((i & 1) == 0) { pk_even0 = p0; pk_even1 = p1; }
-            else __builtin_amdgcn_raw_buffer_store_b128(u32x4{pk_even0, pk_even1, p0, p1}, vrs, voff + 16u * q + 64u * (t >> 1), 0, WC_ST_AUX);
+            else __builtin_amdgcn_raw_buffer_store_b128(u32x4{pk_even0, pk_even1, p0, p1}, R.vrs, voff + 16u * q + 64u * (t >> 1), 0, WC_ST_AUX);
           } else {
-            __builtin_amdgcn_raw_buffer_store_b64(u32x2{p0, p1}, vrs, voff + 8u * q + 32u * t, 0, WC_ST_AUX);
+            __builtin_amdgcn_raw_buffer_store_b64(u32x2{p0, p1}, R.vrs, voff + 8u * q + 32u * t, 0, WC_ST_AUX);
           }
         }
         if ((i & 1) == 1 || i == 2 * PPW) {     // fp32 over a pair's two tiles (the odd last tile alone), as wchain_kernel
@@ -808,12 +810,12 @@ __global__ __launch_bounds__(256, 1) void wchain4_kernel(const WcArgs a) {
     };
 
     double Ecur = 0.0;
-    const bool reeval = STORE && a.burnin > 0;
     __builtin_amdgcn_s_waitcnt(0x0F70);                 // vmcnt(0): retire the prologue's loads (see wchain_kernel)
-    for (int it = -1; it < S + (reeval ? 1 : 0); ++it) {
-      const bool re = reeval && it == a.burnin;
-      const int m = (reeval && it > a.burnin) ? it - 1 : it;
-      const bool step = m >= 0 && !re;
+    const int n_it = vn_chain_passes<STORE>(a.nsamples, a.burnin);
+    for (int it = -1; it < n_it; ++it) {
+      const VnChainPass ps = vn_chain_pass<STORE>(it, a.nsamples, a.burnin);
+      const bool re = ps.re, step = ps.step;
+      const int m = ps.m, slot = ps.slot;
       float zp[8];
       float lu = 0.f;
       if (step) {
@@ -826,9 +828,9 @@ __global__ __launch_bounds__(256, 1) void wchain4_kernel(const WcArgs a) {
           lu = q == 0 ? fast_log(uu) : 0.f;
         } else {
           const unsigned so = (unsigned)m * (unsigned)a.NT;
-          const f32x4 e0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(eps_rs, rp_off + so * (LAT * 4u), 0, 0));
-          const f32x4 e1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(eps_rs, rp_off + so * (LAT * 4u) + 64u, 0, 0));
-          const float uu = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(u_rs, (unsigned)nrow * 4u + so * 4u, 0, 0));
+          const f32x4 e0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(R.eps_rs, rp_off + so * (LAT * 4u), 0, 0));
+          const f32x4 e1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(R.eps_rs, rp_off + so * (LAT * 4u) + 64u, 0, 0));
+          const float uu = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(R.u_rs, (unsigned)nrow * 4u + so * 4u, 0, 0));
 #pragma unroll
           for (int t = 0; t < 4; ++t) { zp[t] = z[t] + a.sd * e0[t]; zp[4 + t] = z[4 + t] + a.sd_hi * e1[t]; }
           lu = q == 0 ? fast_log(uu) : 0.f;
@@ -840,7 +842,6 @@ __global__ __launch_bounds__(256, 1) void wchain4_kernel(const WcArgs a) {
 #pragma unroll
         for (int t = 0; t < 8; ++t) zp[t] = z[t];
       }
-      const int slot = !STORE ? -1 : (re ? a.nsamples : (m >= a.burnin ? m - a.burnin : ((m < 0 && a.burnin == 0) ? a.nsamples : -1)));
       double Ep;
       if (STORE && slot >= 0) Ep = energy(zp, slot, std::true_type{});
       else Ep = energy(zp, slot, std::false_type{});
@@ -852,7 +853,7 @@ __global__ __launch_bounds__(256, 1) void wchain4_kernel(const WcArgs a) {
       lu = sum_rows4(lu);
       const float accp = (float)(Ecur - Ep) + 0.5f * pr;
       const bool ok = m < 0 || lu < accp;
-      if (a.acc_out && m >= 0) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, accp), acc_rs, fr_off + (unsigned)m * (unsigned)a.NT * 4u, 0, 0);
+      if (a.acc_out && m >= 0) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, accp), R.acc_rs, fr_off + (unsigned)m * (unsigned)a.NT * 4u, 0, 0);
 #pragma unroll
       for (int j = 0; j < 8; ++j) z[j] = ok ? zp[j] : z[j];
       Ecur = ok ? Ep : Ecur;
@@ -860,18 +861,14 @@ __global__ __launch_bounds__(256, 1) void wchain4_kernel(const WcArgs a) {
         const unsigned r = (unsigned)(m - a.burnin);
         if (STORE) {
           cur_src = ok ? (int)r : cur_src;
-          __builtin_amdgcn_raw_buffer_store_b32((unsigned)cur_src, src_rs, fr_off + r * (unsigned)a.NT * 4u, 0, 0);
+          __builtin_amdgcn_raw_buffer_store_b32((unsigned)cur_src, R.src_rs, fr_off + r * (unsigned)a.NT * 4u, 0, 0);
         }
         const unsigned zo = zs_off + r * (LAT * 4u);
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{z[0], z[1], z[2], z[3]}), zs_rs, zo, 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{z[4], z[5], z[6], z[7]}), zs_rs, zo + 64u, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{z[0], z[1], z[2], z[3]}), R.zs_rs, zo, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{z[4], z[5], z[6], z[7]}), R.zs_rs, zo + 64u, 0, 0);
       }
     }
-    if (a.update_Z) {
-      const unsigned zo = (fvalid && w0) ? rp_off : WC_OOB;
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{z[0], z[1], z[2], z[3]}), z_rs, zo, 0, 0);
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{z[4], z[5], z[6], z[7]}), z_rs, zo + 64u, 0, 0);
-    }
+    wc_store_z(a, R, fr, rp_off, z);
   }
 }
 
@@ -882,23 +879,32 @@ __global__ __launch_bounds__(256, 1) void wchain4_kernel(const WcArgs a) {
 // ============================================================================
 namespace {
 
-template <int MAXT, bool EXACT, bool SPLIT, bool STORE, int NWAVES, bool LOL, bool HIALL, bool M2, int GT = 0>
-int wc_launch(const WcArgs& a, int grid, size_t lds, hipStream_t st) {
-  auto* fn = wchain_kernel<MAXT, EXACT, SPLIT, STORE, NWAVES, LOL, HIALL, M2, GT>;
-  if (int e = vn_ensure_dyn_lds((const void*)fn, VN_LDS_LIMIT)) return e;
-  hipLaunchKernelGGL(fn, dim3(grid), dim3(NWAVES * 64), lds, st, a);
-  return 0;
+// (a.B1, a.VsS) -> the <M2, STORE> instantiation: go(std::bool_constant<M2>, std::bool_constant<STORE>) launches it
+template <typename Go>
+int wc_by_m2_store(const WcArgs& a, Go&& go) {
+  if (a.B1) return a.VsS ? go(std::true_type{}, std::true_type{}) : go(std::true_type{}, std::false_type{});
+  return a.VsS ? go(std::false_type{}, std::true_type{}) : go(std::false_type{}, std::false_type{});
 }
 // M1 runs NW1 wavefronts per workgroup; M2 the same (at 8 the per-frame layer-1 bias rows live in LDS: b1_lds)
 template <int MAXT, bool EXACT, bool SPLIT, int NW1, bool LOL, int GT = 0>
 int wc_launch_s(const WcArgs& a, int nwt, int n_sms, size_t lds, hipStream_t st) {
   int grid = nwt;                                       // (wave tiles spread over the CUs first, then over a workgroup's wavefronts)
   if (grid > n_sms) grid = n_sms;                       // one workgroup per CU (LDS), wave tiles in a grid-stride loop
-  if (a.B1)
-    return a.VsS ? wc_launch<MAXT, EXACT, SPLIT, true, NW1, LOL, true, true, GT>(a, grid, lds, st)
-                 : wc_launch<MAXT, EXACT, SPLIT, false, NW1, LOL, true, true, GT>(a, grid, lds, st);
-  return a.VsS ? wc_launch<MAXT, EXACT, SPLIT, true, NW1, LOL, true, false, GT>(a, grid, lds, st)
-               : wc_launch<MAXT, EXACT, SPLIT, false, NW1, LOL, true, false, GT>(a, grid, lds, st);
+  return wc_by_m2_store(a, [&](auto m2, auto store) -> int {
+    auto* fn = wchain_kernel<MAXT, EXACT, SPLIT, decltype(store)::value, NW1, LOL, true, decltype(m2)::value, GT>;
+    if (int e = vn_ensure_dyn_lds((const void*)fn, VN_LDS_LIMIT)) return e;
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(NW1 * 64), lds, st, a);
+    return 0;
+  });
+}
+// four wavefronts per wave tile: one workgroup per tile, exchange areas only in LDS
+template <int MAXT>
+int wc_launch4(const WcArgs& a, hipStream_t st) {
+  const size_t lds4 = 2 * 4 * 64 * 16 + 20 * 64 * 4;
+  return wc_by_m2_store(a, [&](auto m2, auto store) -> int {
+    hipLaunchKernelGGL((wchain4_kernel<MAXT, decltype(store)::value, decltype(m2)::value>), dim3(a.n_wtiles), dim3(256), lds4, st, a);
+    return 0;
+  });
 }
 
 }  // namespace
@@ -955,20 +961,7 @@ int vn_launch_wchain(vaenmf_plan* p, const VnChainCall& cc, hipStream_t st) {
   VN_REQUIRE(lds <= (size_t)VN_LDS_LIMIT, "wave chain: %zu bytes of LDS needed", lds);
   // small batches (at most one wave tile per CU) in bf16 mode at 17 / 33 bin tiles: four wavefronts per wave tile (wchain4_kernel)
   if (!split && (p->NT3c == 17 || p->NT3c == 33) && p->n_wtiles <= p->n_sms && vn_switches().wchain4) {
-    const size_t lds4 = 2 * 4 * 64 * 16 + 20 * 64 * 4;          // exchange areas only
-    const int grid = p->n_wtiles;
-    auto go = [&](auto* fn) -> int {
-      hipLaunchKernelGGL(fn, dim3(grid), dim3(256), lds4, st, a);
-      return 0;
-    };
-    a.w3f = p->w3c; a.b3 = p->b3c;
-    int rc4;
-    if (p->NT3c == 17)
-      rc4 = cc.B1 ? (a.VsS ? go(wchain4_kernel<17, true, true>) : go(wchain4_kernel<17, false, true>))
-                  : (a.VsS ? go(wchain4_kernel<17, true, false>) : go(wchain4_kernel<17, false, false>));
-    else
-      rc4 = cc.B1 ? (a.VsS ? go(wchain4_kernel<33, true, true>) : go(wchain4_kernel<33, false, true>))
-                  : (a.VsS ? go(wchain4_kernel<33, true, false>) : go(wchain4_kernel<33, false, false>));
+    const int rc4 = p->NT3c == 17 ? wc_launch4<17>(a, st) : wc_launch4<33>(a, st);
     if (rc4) return rc4;
     VN_CHECK_HIP(hipGetLastError());
     p->last_chain_kernel = 2;

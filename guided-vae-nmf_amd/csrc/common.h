@@ -325,4 +325,32 @@ __device__ __forceinline__ f32x4 normal4(Xs128& st) {
   return o;
 }
 __device__ __forceinline__ float uniform01(Xs128& st) { return (float)(st.next() >> 8) * 5.9604644775390625e-8f; }
+
+// ---- pass schedule of an MH chain (every chain kernel: chain.hip, engine.hip, wide.hip) ----
+// Pass it = -1 evaluates the initial state (mcem.py:392-400); the MH steps m = 0 .. burnin + nsamples - 1 follow.  With the
+// sample-variance store on (STORE) and a burn-in, one more pass right after the burn-in (`re`) evaluates the state the
+// chain is in again -- nothing drawn, nothing decided -- so that its variances are on record.
+// The store's contract, as stream.hip, vaenmf_sample_store_gather and the oracle read it: a pass writes the variances of
+// the state it evaluates to `slot` (-1: none).  Slot r < nsamples holds the proposal of post-burn-in step r; slot nsamples
+// holds the state the chain is in when the burn-in ends (the initial state when there is no burn-in).
+struct VnChainPass {
+  bool re;       // the re-evaluation pass
+  int m;         // MH step of the pass (-1: the initial state; on the re-evaluation pass: burnin, not taken)
+  bool step;     // an MH step: noise is drawn, the proposal decided
+  int slot;
+};
+template <bool STORE>
+__device__ __forceinline__ int vn_chain_passes(int nsamples, int burnin) {      // the loop is for (it = -1; it < passes; ++it)
+  return nsamples + burnin + ((STORE && burnin > 0) ? 1 : 0);
+}
+template <bool STORE>
+__device__ __forceinline__ VnChainPass vn_chain_pass(int it, int nsamples, int burnin) {
+  const bool reeval = STORE && burnin > 0;
+  VnChainPass p;
+  p.re = reeval && it == burnin;
+  p.m = (reeval && it > burnin) ? it - 1 : it;
+  p.step = p.m >= 0 && !p.re;
+  p.slot = !STORE ? -1 : (p.re ? nsamples : (p.m >= burnin ? p.m - burnin : ((p.m < 0 && burnin == 0) ? nsamples : -1)));
+  return p;
+}
 #endif

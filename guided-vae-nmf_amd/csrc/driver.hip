@@ -30,24 +30,15 @@ extern "C" int vaenmf_mh_chain(vaenmf_plan* p, const float* X2, const float* W, 
                "vaenmf_sample_store(plan, max_samples) after vaenmf_bind_batch (no allocation happens in vaenmf_mh_chain)", p->NT, nsamples);
     cc.VsS = p->VsS; cc.VsS_bytes = need_v; cc.src = p->src; cc.Rs = Rs;
   }
-  if (p->wide) {                                        // wide decoder shapes: one kernel for every batch (wide.hip, 64-bit addresses)
+  // wide decoder shapes: one kernel for every batch (wide.hip, 64-bit addresses).  Else wave-private chains (chain.hip)
+  // while every buffer of the batch is within their 32-bit byte offsets; a larger batch (about 300 k frames at 105
+  // samples) runs engine.hip's team kernel, which addresses with 64 bits
+  const bool use_wchain = !p->wide && vn_wchain_supported(p) && vn_wchain_fits(p, cc);
+  VN_REQUIRE(p->wide || use_wchain || Zs != nullptr, "vaenmf_mh_chain: Zs may be NULL only where the wave-private chain kernels run (vaenmf_wchain_addressable)");
+  {                                                     // each launcher records its kernel in last_chain_kernel
     ProfScope ps(p, VN_K_CHAIN, st);
-    if (int e = vn_launch_widechain(p, cc, st)) return e;
-    if (p->store_on) { p->store_R = nsamples; p->store_Rs = nsamples + 1; }
-    return 0;
+    if (int e = p->wide ? vn_launch_widechain(p, cc, st) : use_wchain ? vn_launch_wchain(p, cc, st) : vn_launch_tchain(p, cc, st)) return e;
   }
-  // wave-private chains (chain.hip) while every buffer of the batch is within their 32-bit byte offsets; a larger batch
-  // (about 300 k frames at 105 samples) runs engine.hip's team kernel, which addresses with 64 bits
-  if (vn_wchain_supported(p) && vn_wchain_fits(p, cc)) {
-    ProfScope ps(p, VN_K_CHAIN, st);
-    if (int e = vn_launch_wchain(p, cc, st)) return e;
-    if (p->store_on) { p->store_R = nsamples; p->store_Rs = nsamples + 1; }
-    return 0;
-  }
-  VN_REQUIRE(Zs != nullptr, "vaenmf_mh_chain: Zs may be NULL only where the wave-private chain kernels run (vaenmf_wchain_addressable)");
-  ProfScope ps(p, VN_K_CHAIN, st);
-  if (int e = vn_launch_tchain(p, cc, st)) return e;
-  p->last_chain_kernel = 0;
   if (p->store_on) { p->store_R = nsamples; p->store_Rs = nsamples + 1; }
   return 0;
 }

@@ -622,13 +622,12 @@ __global__ __launch_bounds__(NW * NTEAM * 64) void mh_chain_kernel(const ChainAr
   // later iteration, wait for the previous step's stores instead (vmcnt counts loads and stores in order)
   __builtin_amdgcn_s_waitcnt(0x0F70);                 // vmcnt(0), gfx9 encoding
   double Ecur[2] = {0.0, 0.0};
-  // m = -1 evaluates the initial state, Vs_t = decoder(Z_t) (mcem.py:392-400); m >= 0 are the MH steps.
-  // With the store on and a burn-in, one more pass after the burn-in re-evaluates the state the chain is in
-  // (no noise drawn, nothing decided) so that its variances are on record in slot R.
-  const bool reeval = STORE && a.burnin > 0;
-  for (int it = -1; it < S + (reeval ? 1 : 0); ++it) {
-    const bool re = reeval && it == a.burnin;
-    const int m = (reeval && it > a.burnin) ? it - 1 : it;
+  // the passes of vn_chain_pass (common.h): the initial state, Vs_t = decoder(Z_t), then the MH steps
+  const int n_it = vn_chain_passes<STORE>(a.nsamples, a.burnin);
+  for (int it = -1; it < n_it; ++it) {
+    const VnChainPass ps = vn_chain_pass<STORE>(it, a.nsamples, a.burnin);
+    const bool re = ps.re;
+    const int m = ps.m, slot = ps.slot;
     // ---- proposal  Z' = Z + sqrt(var) * randn   (mcem.py:407)
     float zp[2][8];
     float e8[2][8];
@@ -649,7 +648,6 @@ __global__ __launch_bounds__(NW * NTEAM * 64) void mh_chain_kernel(const ChainAr
     }
     const float uu0 = (m >= 0 && !re) ? L.u[c] : 1.f, uu1 = (m >= 0 && !re) ? L.u[16 + c] : 1.f;
     double Ep[2];
-    const int slot = !STORE ? -1 : (re ? a.nsamples : (m >= a.burnin ? m - a.burnin : ((m < 0 && a.burnin == 0) ? a.nsamples : -1)));
     // mcem.py:410-412 (draws the next step's noise inside); two copies of the evaluation, with and without stores
     if (STORE && slot >= 0) energy(zp, Ep, re ? S : m + 1, slot, std::true_type{});
     else energy(zp, Ep, re ? S : m + 1, slot, std::false_type{});
@@ -1418,6 +1416,7 @@ int vn_launch_tchain(vaenmf_plan* p, const VnChainCall& cc, hipStream_t st) {
   }
   if (lrc) return lrc;
   VN_CHECK_HIP(hipGetLastError());
+  p->last_chain_kernel = 0;
   return 0;
 }
 

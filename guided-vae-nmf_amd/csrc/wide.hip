@@ -248,16 +248,14 @@ __global__ __launch_bounds__(256) void widechain_kernel(const WideArgs a) {
     U = ush[c];
   };
 
-  const int S = a.nsamples + a.burnin;
   double Ecur = 0.0;
   int cur_src = a.nsamples;
-  // m = -1 evaluates the initial state (mcem.py:392-400); m >= 0 are the MH steps.  With the store on and a burn-in, one
-  // more pass after the burn-in evaluates the state the chain is in again so that its variances are on record in slot R.
-  const bool reeval = STORE && a.burnin > 0;
-  for (int it = -1; it < S + (reeval ? 1 : 0); ++it) {
-    const bool re = reeval && it == a.burnin;
-    const int m = (reeval && it > a.burnin) ? it - 1 : it;
-    const bool step = m >= 0 && !re;
+  // the passes of vn_chain_pass (common.h)
+  const int n_it = vn_chain_passes<STORE>(a.nsamples, a.burnin);
+  for (int it = -1; it < n_it; ++it) {
+    const VnChainPass ps = vn_chain_pass<STORE>(it, a.nsamples, a.burnin);
+    const bool re = ps.re, step = ps.step;
+    const int m = ps.m, slot = ps.slot;
     // ---- proposal  Z' = Z + sqrt(var) * randn   (mcem.py:407)
     float e8[8] = {0, 0, 0, 0, 0, 0, 0, 0}, uu = 1.f;
     if (step) {
@@ -282,7 +280,6 @@ __global__ __launch_bounds__(256) void widechain_kernel(const WideArgs a) {
       zp[j] = z[j] + sd * e8[j];
       pr += z[j] * z[j] - zp[j] * zp[j];
     }
-    const int slot = !STORE ? -1 : (re ? a.nsamples : (m >= a.burnin ? m - a.burnin : ((m < 0 && a.burnin == 0) ? a.nsamples : -1)));
     double Ep;
     float P, U;
     if (STORE && slot >= 0) energy(zp, pr, uu, Ep, P, U, slot, std::true_type{});

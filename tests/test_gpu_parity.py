@@ -1516,18 +1516,28 @@ def test_tiny_and_ragged_utterances_against_the_oracle(counts, prec):
         assert nrm_err(sh, o["WFs"] * o["o"].X) < 2e-3
 
 
-@pytest.mark.parametrize("F,K,model,rng,zdim,hdim", [(257, 8, "M1", "device", 32, [128, 128]), (257, 8, "M2", "device", 32, [128, 128]),
-                                                     (257, 8, "M1", "replay", 32, [128, 128]), (513, 10, "M1", "device", 32, [128, 128]),
-                                                     (513, 10, "M2", "device", 32, [128, 128]), (513, 32, "M1", "replay", 32, [128, 128]),
-                                                     # decoder shapes of section 3.8: one hidden layer (two barriers per evaluation), 16 latents
-                                                     (257, 8, "M1", "device", 16, [128]), (513, 10, "M2", "replay", 16, [128])])
-def test_four_wavefront_chain_equals_the_wave_chain_bit_for_bit(F, K, model, rng, zdim, hdim):
+# the first eight ids are the ones these rows had before the store column (pytest numbers a list argument: hdim0 ... hdim7)
+@pytest.mark.parametrize("F,K,model,rng,zdim,hdim,store", [
+    pytest.param(257, 8, "M1", "device", 32, [128, 128], True, id="257-8-M1-device-32-hdim0"),
+    pytest.param(257, 8, "M2", "device", 32, [128, 128], True, id="257-8-M2-device-32-hdim1"),
+    pytest.param(257, 8, "M1", "replay", 32, [128, 128], True, id="257-8-M1-replay-32-hdim2"),
+    pytest.param(513, 10, "M1", "device", 32, [128, 128], True, id="513-10-M1-device-32-hdim3"),
+    pytest.param(513, 10, "M2", "device", 32, [128, 128], True, id="513-10-M2-device-32-hdim4"),
+    pytest.param(513, 32, "M1", "replay", 32, [128, 128], True, id="513-32-M1-replay-32-hdim5"),
+    # decoder shapes of section 3.8: one hidden layer (two barriers per evaluation), 16 latents
+    pytest.param(257, 8, "M1", "device", 16, [128], True, id="257-8-M1-device-16-hdim6"),
+    pytest.param(513, 10, "M2", "replay", 16, [128], True, id="513-10-M2-replay-16-hdim7"),
+    # store off: the kernels' instantiations without row stores
+    pytest.param(257, 8, "M1", "device", 32, [128, 128], False, id="257-8-M1-device-32-h128x128-nostore"),
+    pytest.param(513, 10, "M2", "replay", 16, [128], False, id="513-10-M2-replay-16-h128-nostore")])
+def test_four_wavefront_chain_equals_the_wave_chain_bit_for_bit(F, K, model, rng, zdim, hdim, store):
     """Small batches of the bench shape (at most one 16-frame wave tile per CU: one utterance through the drop-in classes)
     run wchain4_kernel -- four wavefronts per tile, each owning two of the output layer's eight bin-tile pairs, the pair
     energies exchanged through LDS and added in the one-wavefront kernel's order.  Same proposals, same log-acceptances,
     same decisions, same samples, same stored rows as wchain_kernel, bit for bit (mcem.py:371-441) -- ragged utterances
     (tiles of 16, 1, 5 frames), store on, a chain with burn-in and one without, then the M-step over both stores; the bench
-    shape (17 bin tiles) and the reference scripts' 1024-pt STFT (33 bin tiles, four pairs per wavefront)."""
+    shape (17 bin tiles) and the reference scripts' 1024-pt STFT (33 bin tiles, four pairs per wavefront).  With the store
+    off (the kernels' instantiations without row stores) the log-acceptances, samples and Z of both chains are compared."""
     need_gpu()
     from vaenmf import _lib
     R, BI = 30, 30
@@ -1558,24 +1568,30 @@ def test_four_wavefront_chain_equals_the_wave_chain_bit_for_bit(F, K, model, rng
             if model == "M2":
                 eng.set_labels(torch.from_numpy(y))
             eng.Z.copy_(torch.from_numpy(Z0))
-            eng.sample_store(True)
+            eng.sample_store(store)
             kw = dict(eps=torch.from_numpy(eps).to(dev), u=torch.from_numpy(u).to(dev)) if rng == "replay" else dict(call=3)
             out = []
             acc = eng.mh_chain(R, BI, 0.01, want_acc=True, **kw)
             assert _lib.lib().vaenmf_plan_query(eng._plan, _lib.Q_CHAIN_KERNEL) == (2 if four else 1)
-            out += [acc.cpu().numpy().copy(), eng.Zs[:, :R].cpu().numpy().copy(), eng.Z.cpu().numpy().copy(), eng.stored_variances(R).cpu().numpy().copy()]
-            c = eng.m_step_stored().clone()
-            out += [t.cpu().numpy().copy() for t in (eng.W, eng.Ht, eng.g, c)]
+            out += [acc.cpu().numpy().copy(), eng.Zs[:, :R].cpu().numpy().copy(), eng.Z.cpu().numpy().copy()]
+            if store:
+                out.append(eng.stored_variances(R).cpu().numpy().copy())
+                c = eng.m_step_stored().clone()
+                out += [t.cpu().numpy().copy() for t in (eng.W, eng.Ht, eng.g, c)]
             # a chain without burn-in (slot R holds the initial state), Z not updated: the Wiener chain's form
             kw2 = dict(eps=kw["eps"][:R], u=kw["u"][:R]) if rng == "replay" else dict(call=4)
             eng.mh_chain(R, 0, 0.01, update_Z=False, **kw2)
-            out += [eng.Zs[:, :R].cpu().numpy().copy(), eng.Z.cpu().numpy().copy(), eng.stored_variances(R).cpu().numpy().copy()]
+            assert _lib.lib().vaenmf_plan_query(eng._plan, _lib.Q_CHAIN_KERNEL) == (2 if four else 1)
+            out += [eng.Zs[:, :R].cpu().numpy().copy(), eng.Z.cpu().numpy().copy()]
+            if store:
+                out.append(eng.stored_variances(R).cpu().numpy().copy())
             return out
         finally:
             os.environ.pop("VAENMF_WCHAIN4", None)
 
     a, b = run(True), run(False)
-    names = ("acc", "Zs", "Z", "rows", "W", "Ht", "g", "cost", "Zs2", "Z2", "rows2")
+    names = ("acc", "Zs", "Z", "rows", "W", "Ht", "g", "cost", "Zs2", "Z2", "rows2") if store else ("acc", "Zs", "Z", "Zs2", "Z2")
+    assert len(a) == len(b) == len(names)
     assert np.abs(a[1] - Z0[:, None, :]).max() > 0.05            # the chains moved
     for x, yv, name in zip(a, b, names):
         assert np.array_equal(x, yv), name
