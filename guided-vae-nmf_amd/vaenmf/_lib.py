@@ -58,6 +58,10 @@ SIGNATURES = {
     "vaenmf_stft_geometry": (_I, [_I64, _D, _D, _D, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "vaenmf_stft_batch_ex": (_I, [_P, _I, _P, _P, _P, _P, C.POINTER(StftOpts), _I, _P, _P]),
     "vaenmf_istft_batch_ex": (_I, [_P, _I, _I, _P, _P, C.POINTER(StftOpts), _I, _P, _P, _P]),
+    "vaenmf_resample_ratio": (_I, [_I64, _I64, C.POINTER(_I), C.POINTER(_I)]),
+    "vaenmf_resample_length": (_I64, [_I64, _I, _I]),
+    "vaenmf_resample_taps": (_I, [_I, _I, _I, _D, _P]),
+    "vaenmf_resample_batch": (_I, [_P, _I, _P, _P, _I, _I, _I, _D, _P, _P]),
     "vaenmf_lorenz_work_bytes": (_I64, [_I, _I, _I, _I]),
     "vaenmf_lorenz_labels": (_I, [_P, _I, _P, _I, _I, _I, _F, _F, _F, _P, _I, _P, _P, _I64, _P]),
     "vaenmf_wiener_mask": (_I, [_P, _P, _I64, _F, _P, _P]),

@@ -10,6 +10,7 @@ from . import stft as vstft
 from . import metrics as vmet
 from .engine import BatchEngine, decoder_params_from_state, latent_dim_from_state
 from .mcem import _encoder_params
+from .resample import crop_batch, resample_batch
 
 
 def shard(items, world_size, rank):
@@ -37,10 +38,20 @@ class Reconstructor:
                                max_frames=max_frames, max_utts=max_utts, z_dim=latent_dim_from_state(sd))
         self.model = model
 
-    def enhance(self, wav, sample_counts, seeds=None, init_seed=0, y=None, classifier=None, mean=None, std=None):
+    def enhance(self, wav, sample_counts, seeds=None, init_seed=0, y=None, classifier=None, mean=None, std=None, fs_in=None):
         """wav: device float32 [sum T].  Returns (s_hat, n_hat) device float32 [sum T], cost [U,niter] (device).
         M2: give the labels `y` (device [NT,Dy]) or a classifier [(W,b)...] (+ optional mean/std, (F,1)):
-        labels = classifier(normalised |X|^2) > 0.5 as in scripts/evaluate_M2_vad.py:122-131."""
+        labels = classifier(normalised |X|^2) > 0.5 as in scripts/evaluate_M2_vad.py:122-131.
+        fs_in: the rate of `wav` in Hz when it is not the model's (self.fs): the batch is resampled to self.fs
+        (vaenmf.resample_batch), enhanced, and s_hat / n_hat are resampled back to fs_in and cropped to sample_counts;
+        frame_counts and the labels (`y` included) stay at the model rate."""
+        if fs_in is not None and fs_in != self.fs:
+            wav_m, counts_m = resample_batch(wav, sample_counts, fs_in, self.fs, device=self.device)
+            s_hat, n_hat, cost = self.enhance(wav_m, counts_m, seeds=seeds, init_seed=init_seed, y=y, classifier=classifier,
+                                              mean=mean, std=std)
+            s_hat, back = resample_batch(s_hat, counts_m, self.fs, fs_in, device=self.device)
+            n_hat, _ = resample_batch(n_hat, counts_m, self.fs, fs_in, device=self.device)
+            return crop_batch(s_hat, back, sample_counts), crop_batch(n_hat, back, sample_counts), cost
         eng = self.eng
         X, fc = vstft.stft_batch(wav, sample_counts, self.fs, self.wlen_sec, self.hop_percent, Fs=eng.Fs, device=self.device)
         eng.bind(fc, Rcap=max(self.nsE, self.nsW), seeds=seeds)
@@ -81,8 +92,15 @@ class MaskEnhancer:
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.device)
         self.layers = [(t(w), t(b)) for w, b in layers]
 
-    def enhance(self, wav, sample_counts):
-        """wav device float32 [sum T] -> (s_hat device float32 [sum T], soft mask device float32 [NT][F])."""
+    def enhance(self, wav, sample_counts, fs_in=None):
+        """wav device float32 [sum T] -> (s_hat device float32 [sum T], soft mask device float32 [NT][F]).
+        fs_in: the rate of `wav` in Hz when it is not self.fs: resampled to self.fs, enhanced, s_hat resampled back to
+        fs_in and cropped to sample_counts; the mask stays at the model rate."""
+        if fs_in is not None and fs_in != self.fs:
+            wav_m, counts_m = resample_batch(wav, sample_counts, fs_in, self.fs, device=self.device)
+            s_hat, mask = self.enhance(wav_m, counts_m)
+            s_hat, back = resample_batch(s_hat, counts_m, self.fs, fs_in, device=self.device)
+            return crop_batch(s_hat, back, sample_counts), mask
         from ._lib import lib, check, ACT_RELU, ACT_SIGMOID
         ptr = lambda x: x.data_ptr()
         st = torch.cuda.current_stream().cuda_stream

@@ -332,6 +332,37 @@ int vaenmf_istft_batch_ex(const float* S, int32_t n_utt, int32_t n_frames_total,
                           const vaenmf_stft_opts* opts, int32_t Fs, float* work,
                           float* wav_out, void* stream);
 
+/* Rational-ratio resampler -- replaces the librosa.resample calls of python/dataset/qut_database.py and
+ * demand_database.py (preprocess_noise) and lets audio at another rate than the model's enter and leave on the device.
+ * It is scipy.signal.resample_poly(x, up, down, window=('kaiser', beta)) with zero padding in closed form: with
+ * M = max(up, down), half = zeros M and the 2 half + 1 taps
+ *   h[i] = up s[i] w[i] / sum_j s[j] w[j],   t = i - half,   s[i] = sin(pi t / M) / (pi t)  (1 / M at t = 0),
+ *   w[i] = I0(beta sqrt(1 - (t / half)^2)) / I0(beta)                   (scipy's defaults: zeros = 10, beta = 5.0)
+ * an utterance of n_in samples gives n_out = ceil(n_in up / down) samples
+ *   y[m] = sum_n x[n] h[half + m down - n up],   n in [0, n_in) with the tap index in [0, 2 half]
+ * (x is zero outside its own utterance: nothing leaks between the utterances of a batch).  The taps are float64 (built in
+ * long double, I0 by its power series, rounded once), the sum runs in float64 in ascending n and is rounded once to
+ * float32, so an utterance has the same bits in any batch.
+ * vaenmf_resample_ratio, HOST only: up = fs_out / g, down = fs_in / g, g = gcd(fs_in, fs_out), rates in Hz; -1 for a rate
+ *   <= 0, -3 when up or down exceeds 1024 (the message names the limit).
+ * vaenmf_resample_length, HOST only: ceil(n_in up / down), or -1 on bad arguments.
+ * vaenmf_resample_taps, HOST only: h HOST float64 [2 zeros max(up, down) + 1], natural order, for up / down AS GIVEN (it
+ *   does not reduce them) -- the values vaenmf_resample_batch uploads for its reduced ratio.  up, down <= 1024 (else -3),
+ *   zeros in [1, 64], beta in [0, 100].
+ * vaenmf_resample_batch: x DEV float [in_offsets[n_utt]], y DEV float [out_offsets[n_utt]], natural (4-byte) alignment,
+ *   read and written element by element: no read leaves [in_offsets[u], in_offsets[u+1]), no write leaves [out_offsets[u],
+ *   out_offsets[u+1]).  in_offsets / out_offsets HOST int64 [n_utt+1], non-decreasing; the ratio is reduced by its gcd
+ *   first, and every out_offsets[u+1] - out_offsets[u] must equal vaenmf_resample_length of the utterance's input length
+ *   (else -1).  up == down is one device copy; n_utt == 0 and empty utterances are no-ops.  The tap table is built and
+ *   uploaded at the first call with a (device, up, down, zeros, beta), the workgroup-to-utterance table at the first call
+ *   with a batch shape (the offsets and the ratio; the 16 most recent shapes are kept): those calls allocate and wait for
+ *   the upload, every later one only launches. */
+int vaenmf_resample_ratio(int64_t fs_in, int64_t fs_out, int32_t* up, int32_t* down);
+int64_t vaenmf_resample_length(int64_t n_in, int32_t up, int32_t down);
+int vaenmf_resample_taps(int32_t up, int32_t down, int32_t zeros, double beta, double* h);
+int vaenmf_resample_batch(const float* x, int32_t n_utt, const int64_t* in_offsets, const int64_t* out_offsets,
+                          int32_t up, int32_t down, int32_t zeros, double beta, float* y, void* stream);
+
 /* Label / guide front-ends of the M2 path -- replace python/processing/target.py.
  * vaenmf_lorenz_labels: clean_speech_IBM (target.py:7-28, mode VAENMF_LABEL_IBM) and
  * clean_speech_VAD (:30-50, mode VAENMF_LABEL_VAD) for a batch of utterances: power =
