@@ -890,6 +890,8 @@ template <int MAXT, bool EXACT, bool SPLIT, int NW1, bool LOL, int GT = 0>
 int wc_launch_s(const WcArgs& a, int nwt, int n_sms, size_t lds, hipStream_t st) {
   int grid = nwt;                                       // (wave tiles spread over the CUs first, then over a workgroup's wavefronts)
   if (grid > n_sms) grid = n_sms;                       // one workgroup per CU (LDS), wave tiles in a grid-stride loop
+  const int cap = vn_switches().grid_cap;               // (tests: a small grid makes every wavefront walk several wave tiles)
+  if (cap > 0 && cap < grid) grid = cap;
   return wc_by_m2_store(a, [&](auto m2, auto store) -> int {
     auto* fn = wchain_kernel<MAXT, EXACT, SPLIT, decltype(store)::value, NW1, LOL, true, decltype(m2)::value, GT>;
     if (int e = vn_ensure_dyn_lds((const void*)fn, VN_LDS_LIMIT)) return e;

@@ -150,6 +150,8 @@ struct VnSwitches {
   bool wfused;         // VAENMF_WFUSED=0: W statistics + W update as two kernels
   bool wgroup;         // VAENMF_WGROUP=0: small batches stay on wstats_fused_kernel instead of wstats_group_kernel
   int wfused_grid;     // VAENMF_WFUSED_GRID=n: at most n workgroups for wstats_fused_kernel (0: no cap)
+  int grid_cap;        // VAENMF_GRID_CAP=n: at most n workgroups for the persistent kernels -- wchain_kernel, decode_kernel, the streaming
+                       // kernels of stream.hip -- so that a small batch walks their tile / frame loops several times (tests; 0: no cap)
   bool keep_zs;        // VAENMF_KEEP_ZS=1: the E-step chains of the sample-store path record their samples anyway
 };
 

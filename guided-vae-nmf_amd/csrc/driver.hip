@@ -132,6 +132,7 @@ VnEmGraphs::Key em_graph_key(const vaenmf_plan* p, const EmCall& c, bool stored,
       u64(p->wpart64), u64(p->wpart16), u64(p->d_t64_n0), u64(p->d_t64_cnt), u64(p->d_t64_first), u64(p->d_t64_g0), (uint64_t)p->n_t64,
       (uint64_t)p->cfg.precision, (uint64_t)p->cfg.K, (uint64_t)p->cfg.F,
       (uint64_t)sw.wchain4, (uint64_t)sw.team_chain, (uint64_t)sw.wfused, (uint64_t)sw.wgroup, (uint64_t)(uint32_t)sw.wfused_grid,
+      (uint64_t)(uint32_t)sw.grid_cap,
       (uint64_t)sw.keep_zs};
 }
 }  // namespace

@@ -1374,7 +1374,9 @@ int launch_decode_kp(DecodeArgs a, int Kp, int grid, hipStream_t st) {
 template <int MODE>
 int launch_decode(const vaenmf_plan* p, const DecodeArgs& a, hipStream_t st) {
   const int want = p->n_sms * 2;
-  const int grid = a.n_tiles < want ? a.n_tiles : want;
+  int grid = a.n_tiles < want ? a.n_tiles : want;
+  const int cap = vn_switches().grid_cap;               // (tests: a small grid makes every workgroup walk several tiles)
+  if (cap > 0 && cap < grid) grid = cap;
   const bool split = p->cfg.precision == VAENMF_PREC_BF16X3;
   const int Kp = (MODE == MODE_STORE) ? 8 : p->Kp;
   switch (p->geom) {

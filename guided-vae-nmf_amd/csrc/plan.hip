@@ -34,6 +34,7 @@ VnSwitches vn_switches() {
   s.wfused = env("VAENMF_WFUSED")[0] != '0';
   s.wgroup = env("VAENMF_WGROUP")[0] != '0';
   s.wfused_grid = atoi(env("VAENMF_WFUSED_GRID"));
+  s.grid_cap = atoi(env("VAENMF_GRID_CAP"));
   s.keep_zs = env("VAENMF_KEEP_ZS")[0] == '1';
   return s;
 }

@@ -1328,6 +1328,8 @@ int launch_stream(const vaenmf_plan* p, StreamArgs a, const StreamForm& f, hipSt
   // H/g is indifferent (4: 0.287, 8: 0.291, 16: 0.305)
   int grid = p->n_sms * 4;
   if (grid * 4 > p->NT) grid = (p->NT + 3) / 4;
+  const int cap = vn_switches().grid_cap;               // (tests: a small grid gives every wavefront a block of several frames)
+  if (cap > 0 && cap < grid) grid = cap;
   const int rc = with_form(f, [&](auto nch, auto kp, auto row) -> int {
     constexpr int NCH = decltype(nch)::value, KP = decltype(kp)::value;
     using ST = typename decltype(row)::type;
@@ -1345,6 +1347,7 @@ int launch_stream(const vaenmf_plan* p, StreamArgs a, const StreamForm& f, hipSt
         if (f.pipelined) {
           int g2 = a.n_sms * 2;
           if (g2 * 4 > a.NT) g2 = (a.NT + 3) / 4;
+          if (cap > 0 && cap < g2) g2 = cap;
           return go(wstats_stream2_kernel<NCH, KP, ST, 0>, g2);
         }
       }

@@ -91,6 +91,64 @@ def shape_class(F, K, precision, n_wave_tiles, R=30, n_cus=256):
                 w_in_lds=Kp <= 8 or Fs * Kp * 4 <= 72 * 1024, w_fused=w_fused)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# The persistent loops, restated: which frames / wave tiles / tiles a wavefront or workgroup walks, trip by trip.  `cap` is
+# VAENMF_GRID_CAP (0: none).  tests/test_persistent_loops_cpu.py checks what the capped cases reach with these.
+def wave_tiles(counts):
+    """plan.hip, vaenmf_bind_batch_async: the 16-frame wave tiles of a batch, [(utterance, first frame, frames)]."""
+    off = np.concatenate([[0], np.cumsum(counts)])
+    return [(u, int(n), int(min(16, off[u + 1] - n))) for u in range(len(counts)) for n in range(off[u], off[u + 1], 16)]
+
+
+def decode_tiles(counts, geom):
+    """plan.hip: the tiles of decode_kernel, 64 frames with two teams (geometries 0 and 3), else 32."""
+    tf = 64 if geom in (0, 3) else 32
+    off = np.concatenate([[0], np.cumsum(counts)])
+    return [(u, int(n), int(min(tf, off[u + 1] - n))) for u in range(len(counts)) for n in range(off[u], off[u + 1], tf)]
+
+
+def stream_grid(NT, n_cus, cap=0, pipelined=False):
+    """stream.hip, launch_stream: workgroups (of four wavefronts) of the streaming kernels; pipelined: wstats_stream2_kernel."""
+    grid = min((2 if pipelined else 4) * n_cus, (NT + 3) // 4)
+    return cap if 0 < cap < grid else grid
+
+
+def wave_frames(NT, grid, wpb=4):
+    """stream.hip, wave_frames: (per, [(n_beg, n_end) per wavefront, workgroup-major]); n_beg >= n_end: no frames."""
+    nw = grid * wpb
+    per = (NT + nw - 1) // nw
+    return per, [(gw * per, min(gw * per + per, NT)) for gw in range(nw)]
+
+
+def chain_waves(precision, chain_tiles):
+    """chain.hip, vn_launch_wchain: wavefronts of a wchain_kernel workgroup."""
+    return 4 if (precision == "bf16x3" or chain_tiles == 33) else 8
+
+
+def chain_grid(n_wave_tiles, n_cus, cap=0):
+    """chain.hip, wc_launch_s."""
+    grid = min(n_wave_tiles, n_cus)
+    return cap if 0 < cap < grid else grid
+
+
+def chain_rounds(n_wave_tiles, grid, nwaves):
+    """chain.hip, wchain_kernel: {(workgroup, wavefront): [wave tile of round 0, 1, ..]}; tile (i nwaves + w) grid + b."""
+    rounds = (n_wave_tiles + grid * nwaves - 1) // (grid * nwaves)
+    return {(b, w): [wt for wt in ((i * nwaves + w) * grid + b for i in range(rounds)) if wt < n_wave_tiles]
+            for b in range(grid) for w in range(nwaves)}, rounds
+
+
+def decode_grid(n_tiles, n_cus, cap=0):
+    """engine.hip, launch_decode."""
+    grid = min(n_tiles, 2 * n_cus)
+    return cap if 0 < cap < grid else grid
+
+
+def decode_trips(n_tiles, grid):
+    """engine.hip, decode_kernel: [tiles of workgroup b, in the order of its trips]."""
+    return [list(range(b, n_tiles, grid)) for b in range(grid)]
+
+
 def test_sweep_reaches_every_dispatch_class():
     """No GPU: the sweep holds at least one F for every kernel form that no 16k + 1 shape reaches, and every F % 4."""
     x3 = [shape_class(F, K, "bf16x3", N_WAVE_TILES, R) for F, K, R in X3_CASES]
@@ -136,27 +194,29 @@ def test_sweep_reaches_every_dispatch_class():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-def _inputs(F, K, R, Dy=0):
-    """The recipe of test_m_step_and_chain_other_shapes: ragged batch, tilted spectrogram, Xavier decoder."""
+def _inputs(F, K, R, Dy=0, counts=None, seed=None):
+    """The recipe of test_m_step_and_chain_other_shapes: ragged batch, tilted spectrogram, Xavier decoder.  counts: the
+    frames per utterance (COUNTS); seed: the generator seed of the inputs (SEEDS, else 1000 + F)."""
     params = orc.xavier_normal_params([F, 32, [128, 128]], seed=7, y_dim=Dy, bias_std=0.05)
-    g = np.random.default_rng(SEEDS.get((F, K, R), 1000 + F))
-    NT = sum(COUNTS)
-    c = SimpleNamespace(F=F, K=K, R=R, Dy=Dy, params=params, NT=NT, S_steps=6, ns=3)
-    c.Xs = [((g.standard_normal((n, F)) + 1j * g.standard_normal((n, F))) * (0.5 + 3 * np.exp(-np.arange(F) / 60.0))).astype(np.complex64) for n in COUNTS]
-    c.W0 = [np.maximum(g.random((F, K)), 1e-8).astype(np.float32) for _ in COUNTS]
-    c.H0 = [np.maximum(g.random((K, n)), 1e-8).astype(np.float32) for n in COUNTS]
-    c.ys = [(g.random((n, Dy)) > 0.5).astype(np.float32) for n in COUNTS] if Dy else [None] * len(COUNTS)
+    g = np.random.default_rng(SEEDS.get((F, K, R), 1000 + F) if seed is None else seed)
+    counts = list(COUNTS if counts is None else counts)
+    NT = sum(counts)
+    c = SimpleNamespace(F=F, K=K, R=R, Dy=Dy, params=params, NT=NT, S_steps=6, ns=3, counts=counts)
+    c.Xs = [((g.standard_normal((n, F)) + 1j * g.standard_normal((n, F))) * (0.5 + 3 * np.exp(-np.arange(F) / 60.0))).astype(np.complex64) for n in counts]
+    c.W0 = [np.maximum(g.random((F, K)), 1e-8).astype(np.float32) for _ in counts]
+    c.H0 = [np.maximum(g.random((K, n)), 1e-8).astype(np.float32) for n in counts]
+    c.ys = [(g.random((n, Dy)) > 0.5).astype(np.float32) for n in counts] if Dy else [None] * len(counts)
     c.Zs = (0.7 * g.standard_normal((NT, R, 32))).astype(np.float32)
     c.gains = (0.5 + g.random(NT)).astype(np.float32)
     c.eps = g.standard_normal((c.S_steps, NT, 32)).astype(np.float32)
     c.uu = g.random((c.S_steps, NT)).astype(np.float32)
     c.Z0 = (0.5 * g.standard_normal((NT, 32))).astype(np.float32)
-    c.off = np.concatenate([[0], np.cumsum(COUNTS)])
+    c.off = np.concatenate([[0], np.cumsum(counts)])
     return c
 
 
 def _engine(c, precision, Rcap=None, seeds=None):
-    eng = make_engine(c.params, c.F, c.K, COUNTS, Rcap=Rcap or c.R, precision=precision, seeds=seeds)
+    eng = make_engine(c.params, c.F, c.K, c.counts, Rcap=Rcap or c.R, precision=precision, seeds=seeds)
     eng.set_spectrogram(c.Xs)
     eng.init_nmf(c.W0, c.H0)
     if c.Dy:
