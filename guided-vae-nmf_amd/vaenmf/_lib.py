@@ -62,6 +62,10 @@ SIGNATURES = {
     "vaenmf_resample_length": (_I64, [_I64, _I, _I]),
     "vaenmf_resample_taps": (_I, [_I, _I, _I, _D, _P]),
     "vaenmf_resample_batch": (_I, [_P, _I, _P, _P, _I, _I, _I, _D, _P, _P]),
+    "vaenmf_segment_count": (_I, [_I, _P, _I, _I, C.POINTER(_I64), C.POINTER(_I64)]),
+    "vaenmf_segment_table": (_I, [_I, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vaenmf_gather_rows": (_I, [_P, _P, _I64, _I, _P, _P]),
+    "vaenmf_blend_rows": (_I, [_P, _P, _P, _P, _I64, _I, _P, _P]),
     "vaenmf_lorenz_work_bytes": (_I64, [_I, _I, _I, _I]),
     "vaenmf_lorenz_labels": (_I, [_P, _I, _P, _I, _I, _I, _F, _F, _F, _P, _I, _P, _P, _I64, _P]),
     "vaenmf_wiener_mask": (_I, [_P, _P, _I64, _F, _P, _P]),

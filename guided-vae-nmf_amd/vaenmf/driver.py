@@ -82,14 +82,17 @@ def _from_rate(wav, counts, rates, lengths, fs, device):
 
 def evaluate(rec: Reconstructor, file_paths, processed_data_dir, output_data_dir, batch_size=64,
              world_size=1, rank=0, classifier=None, mean=None, std=None, seed=0, label_source="dnn", label_type="ibm",
-             quantile_fraction=0.999, quantile_weight=0.999, resample=False):
+             quantile_fraction=0.999, quantile_weight=0.999, resample=False, segment_sec=None, overlap_sec=2.0):
     """Enhance this rank's shard of `file_paths`; returns the list of written (s_est, n_est) paths.
     M2: labels from `label_source` ('dnn' needs `classifier`; 'oracle' reads the clean speech; 'timo' the SPP
     estimator), `label_type` 'ibm' (y_dim F) or 'vad' (y_dim 1); M1 ignores them.
     resample: False refuses a file whose rate is not rec.fs (ValueError, as the reference does).  True takes files at any
     rates vaenmf.resample_batch supports: they are resampled to rec.fs on the device (one call per rate of a batch),
     enhanced together, and every file's estimates are written at its own rate and length; labels and frame counts are
-    those of the model rate.  A file at rec.fs passes through untouched, with the bits resample=False gives it."""
+    those of the model rate.  A file at rec.fs passes through untouched, with the bits resample=False gives it.
+    segment_sec: None enhances every file as one utterance (rec.enhance).  A value sends the batch through
+    rec.enhance_long(segment_sec=, overlap_sec=): files of any length, cut into overlapping segments on the frame grid; the
+    same files are written, the label dumps per file in its own frame order."""
     from . import target as vtarget
     from . import spp_estimation as vspp
     if label_source not in ("dnn", "oracle", "timo"):
@@ -135,8 +138,12 @@ def evaluate(rec: Reconstructor, file_paths, processed_data_dir, output_data_dir
             y = (y_soft > 0.5).float()
         elif m2 and classifier is None:
             raise ValueError("label_source='dnn' needs a classifier")
-        s_hat, n_hat, _ = rec.enhance(wav, counts, seeds=seeds, init_seed=seed, y=y,
-                                      classifier=classifier if (m2 and label_source == "dnn") else None, mean=mean, std=std)
+        clf = classifier if (m2 and label_source == "dnn") else None
+        if segment_sec is None:
+            s_hat, n_hat, _ = rec.enhance(wav, counts, seeds=seeds, init_seed=seed, y=y, classifier=clf, mean=mean, std=std)
+        else:
+            s_hat, n_hat, _ = rec.enhance_long(wav, counts, segment_sec, overlap_sec, seeds=seeds, init_seed=seed, y=y,
+                                               classifier=clf, mean=mean, std=std)
         if m2 and label_source == "dnn":
             y_soft, y = rec.y_soft, rec.y_hard
         if resample:

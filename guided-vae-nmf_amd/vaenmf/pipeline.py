@@ -52,9 +52,21 @@ class Reconstructor:
             s_hat, back = resample_batch(s_hat, counts_m, self.fs, fs_in, device=self.device)
             n_hat, _ = resample_batch(n_hat, counts_m, self.fs, fs_in, device=self.device)
             return crop_batch(s_hat, back, sample_counts), crop_batch(n_hat, back, sample_counts), cost
+        X, fc = vstft.stft_batch(wav, sample_counts, self.fs, self.wlen_sec, self.hop_percent, Fs=self.eng.Fs, device=self.device)
+        S, N, cost = self.em(X, fc, seeds=seeds, init_seed=init_seed, y=y, classifier=classifier, mean=mean, std=std)
+        nfft, hop = vstft.frame_geometry(sample_counts[0], self.fs, self.wlen_sec, self.hop_percent)[:2]
+        s_hat = vstft.istft_batch(S, fc, sample_counts, nfft, hop, device=self.device)
+        n_hat = vstft.istft_batch(N, fc, sample_counts, nfft, hop, device=self.device)
+        self.frame_counts = fc
+        return s_hat, n_hat, cost
+
+    def em(self, X, frame_counts, seeds=None, init_seed=0, y=None, classifier=None, mean=None, std=None):
+        """The frame-domain middle of enhance(): X device float32 [NT,Fs,2] (the STFT rows of the utterances, concatenated;
+        padding bins zero), frame_counts per utterance.  Returns (S, N) device [NT,Fs,2], the Wiener-filtered speech and
+        noise spectrograms, and cost [U,niter] (device).  y / classifier / mean / std as in enhance(); with a classifier
+        self.y_soft / self.y_hard are set."""
         eng = self.eng
-        X, fc = vstft.stft_batch(wav, sample_counts, self.fs, self.wlen_sec, self.hop_percent, Fs=eng.Fs, device=self.device)
-        eng.bind(fc, Rcap=max(self.nsE, self.nsW), seeds=seeds)
+        eng.bind(frame_counts, Rcap=max(self.nsE, self.nsW), seeds=seeds)
         eng.set_spectrogram(X)
         # W = max(rand(F,K), eps), H = max(rand(K,N), eps), g = 1 (mcem.py:42-44, :51): the library's generator, keyed by
         # the utterance seeds (an utterance's start does not depend on the batch it sits in)
@@ -66,11 +78,27 @@ class Reconstructor:
             eng.set_labels(y)
         eng.encode(self.enc, y)
         cost, S, N = eng.run(self.niter, self.nsE, self.biE, self.nsW, self.biW, self.var_RW, store=self.store)
-        nfft, hop = vstft.frame_geometry(sample_counts[0], self.fs, self.wlen_sec, self.hop_percent)[:2]
-        s_hat = vstft.istft_batch(S, fc, sample_counts, nfft, hop, device=self.device)
-        n_hat = vstft.istft_batch(N, fc, sample_counts, nfft, hop, device=self.device)
-        self.frame_counts = fc
-        return s_hat, n_hat, cost
+        return S, N, cost
+
+    def enhance_long(self, wav, sample_counts, segment_sec=30.0, overlap_sec=2.0, seeds=None, init_seed=0, y=None, classifier=None,
+                     mean=None, std=None, fs_in=None):
+        """enhance() for recordings of any length (vaenmf.longform): one STFT of the batch, its frames cut into segments of
+        L = floor(segment_sec fs / hop) frames that overlap by V = floor(overlap_sec fs / hop) (the rule: include/vaenmf.h),
+        every segment an utterance of em() -- rounds of as many as the engine holds -- the S / N rows of neighbouring
+        segments blended across their overlap, one iSTFT.  Returns (s_hat, n_hat) as enhance() does and cost, a list with
+        one [segments of the recording, niter] tensor per recording.  A recording of fewer than 2 L - V frames is one
+        segment: a batch of such recordings gets the bits of enhance().
+        seeds: per recording; segment 0 runs with the recording's seed, segment j >= 1 with longform.segment_seeds' mix.
+        y: device [NT,Dy] in recording frame order.  With a classifier the labels are computed per segment and
+        self.y_soft / self.y_hard come back in recording order, an overlap frame taking the segment with the larger weight
+        (the earlier one on a tie).  Sets self.frame_counts (per recording), self.segments (the table), self.S_frames /
+        self.N_frames (the blended spectrograms, device [NT,Fs,2]).  ValueError when overlap_sec > segment_sec / 2, L < 2
+        or the engine's max_frames is below the longest possible segment, 2 L - V - 1 frames.
+        The defaults, 30 s segments and 2 s overlaps, are a judgment: their effect on SI-SDR has not been measured
+        beyond the one run in DESIGN 3.5c."""
+        from . import longform
+        return longform.enhance_long(self, wav, sample_counts, segment_sec, overlap_sec, seeds=seeds, init_seed=init_seed, y=y,
+                                     classifier=classifier, mean=mean, std=std, fs_in=fs_in)
 
 
 class MaskEnhancer:

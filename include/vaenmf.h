@@ -363,6 +363,49 @@ int vaenmf_resample_taps(int32_t up, int32_t down, int32_t zeros, double beta, d
 int vaenmf_resample_batch(const float* x, int32_t n_utt, const int64_t* in_offsets, const int64_t* out_offsets,
                           int32_t up, int32_t down, int32_t zeros, double beta, float* y, void* stream);
 
+/* Long recordings as batches of short utterances (no reference counterpart: its scripts process utterances of a few
+ * seconds).  A recording of n frames is cut on the frame grid into segments of L >= 2 frames that overlap by V frames,
+ * 0 <= V <= L / 2: stride = L - V, m = max(1, floor((n - V) / stride)) segments, segment k starts at frame k stride,
+ * segments 0 .. m-2 have L frames and the last one runs to frame n (n frames when m = 1, else L <= length < L + stride).
+ * A recording of fewer than L + stride frames is one segment; every frame lies in one segment or in two consecutive ones,
+ * every overlap has exactly V frames.  The i-th frame of an overlap (i = 0 .. V-1) is blended with the weight
+ * w_b = float((i + 1) / (V + 1)) (double, rounded once) for the later segment and w_a = 1.0f - w_b (float) for the earlier.
+ * Processing order of the segments of a batch: first every segment of L frames that is not its recording's last (recording
+ * order, then segment order), then the recordings' last segments in recording order.  Segment rows are the frames of the
+ * segments concatenated in that order; recording-order frames are the frames of the recordings concatenated.
+ * vaenmf_segment_count, HOST only: frame_counts HOST int32 [n_utt], each >= 1.  *n_segments = sum of m, *n_segment_rows =
+ *   sum of (n + (m - 1) V).  -1 (the message names the numbers) for L < 2, V < 0 or V > L / 2, or an empty recording.
+ * vaenmf_segment_table, HOST only: fills, in processing order,
+ *   seg_utt, seg_index, seg_first, seg_len  HOST int32 [n_segments]: the segment's recording, its index j inside the
+ *                                           recording, its first frame j stride inside the recording, its length;
+ *   src_row  HOST int32 [n_segment_rows]    the recording-order frame every segment row copies;
+ *   row_a, row_b  HOST int32, w_b HOST float, [sum of frame_counts]: per recording-order frame the segment row that holds
+ *                                           it -- row_b = -1 and w_b = 0 for a frame with one owner; in an overlap row_a is
+ *                                           the earlier segment's row, row_b the later one's and w_b the later one's weight.
+ *   Every array is written in full and nothing beside it.  Beyond the refusals of vaenmf_segment_count: -1 when the longest
+ *   possible segment, L + stride - 1 frames, exceeds max_frames (the capacity of the plan that will run the segments), or
+ *   when the segment rows exceed 2^31 - 1.
+ * vaenmf_gather_rows: dst[r] = src[row_map[r]] for r < n_rows, rows of row_floats floats.  src DEV float [rows][row_floats]
+ *   with rows > max(row_map) (the caller's duty: the map is not checked on the device), row_map DEV int32 [n_rows] (repeats
+ *   allowed), dst DEV float [n_rows][row_floats], not overlapping src.  Rows are moved bit for bit, padding included.
+ * vaenmf_blend_rows: for t < n_frames, dst[t] = seg[row_a[t]] bit for bit when row_b[t] < 0, else per float
+ *   (1.0f - w_b[t]) seg[row_a[t]] + w_b[t] seg[row_b[t]] with each product rounded to float32 and then their sum (no fused
+ *   multiply-add): the same bits whichever of the two operands is called a.  seg DEV float [rows][row_floats], row_a,
+ *   row_b DEV int32 [n_frames], w_b DEV float [n_frames] (not read where row_b < 0), dst DEV float [n_frames][row_floats],
+ *   not overlapping seg.  Padding bins need no mask: zeros blend to zeros.
+ * Both kernels take any row_floats >= 0 and buffers of exactly the extents stated at their natural (4-byte) alignment:
+ *   16-byte accesses are used when row_floats is a multiple of 4 and both float buffers are 16-byte aligned, float
+ *   accesses otherwise.  No plan, no allocation, no synchronisation; every output row is written by its own lanes alone
+ *   (no atomics), so a row's value does not depend on what else the call moves.  n_rows / n_frames = 0 is a no-op. */
+int vaenmf_segment_count(int32_t n_utt, const int32_t* frame_counts, int32_t L, int32_t V, int64_t* n_segments,
+                         int64_t* n_segment_rows);
+int vaenmf_segment_table(int32_t n_utt, const int32_t* frame_counts, int32_t L, int32_t V, int32_t max_frames,
+                         int32_t* seg_utt, int32_t* seg_index, int32_t* seg_first, int32_t* seg_len, int32_t* src_row,
+                         int32_t* row_a, int32_t* row_b, float* w_b);
+int vaenmf_gather_rows(const float* src, const int32_t* row_map, int64_t n_rows, int32_t row_floats, float* dst, void* stream);
+int vaenmf_blend_rows(const float* seg, const int32_t* row_a, const int32_t* row_b, const float* w_b, int64_t n_frames,
+                      int32_t row_floats, float* dst, void* stream);
+
 /* Label / guide front-ends of the M2 path -- replace python/processing/target.py.
  * vaenmf_lorenz_labels: clean_speech_IBM (target.py:7-28, mode VAENMF_LABEL_IBM) and
  * clean_speech_VAD (:30-50, mode VAENMF_LABEL_VAD) for a batch of utterances: power =
