@@ -49,8 +49,11 @@ struct WcArgs {
   int F, Fs;
   const float *X2, *W, *Ht, *g, *B1, *Vb;
   float *Z, *Zs, *acc_out;
-  void* VsS;                       // sample-variance store [NT+1][Rs][Fs] (float: bf16x3 mode, bf16: bf16 mode) or null
+  void* VsS;                       // sample-variance store (float: bf16x3 mode, bf16: bf16 mode), NT + 1 frame blocks laid out as `lay`, or null
   unsigned VsS_bytes;
+  VnStoreLayout lay;               // (common.h)
+  int park_lds;                    // line-aligned layout: byte offset in LDS of the areas that collect the odd bins F-1, one per wavefront
+                                   // that writes them, [16 frames][lay.xframe elements] -- a frame's block as it goes to the store
   int32_t* src;                    // [Rs][NT]
   int Rs;
   const int32_t *wt_utt, *wt_n0, *wt_cnt;   // wave tiles: <= 16 frames of one utterance
@@ -205,6 +208,53 @@ __device__ __forceinline__ void wc_store_z(const WcArgs& a, const WcRes& R, cons
   }
 }
 
+// Line-aligned store layout (ALN): the rows end at bin F-2 and the last bin tile, whose only real bin F-1 sits in lane
+// (q = 0, c) for frame c, is not stored.  That lane parks the value in the wavefront's LDS area at every stored pass (one
+// 2- or 4-byte LDS write), and after the last pass the wavefront writes each frame's block of odd bins once, in 16-byte
+// pieces -- lane (q, c): pieces q, q + 4, ... of frame c.  (Written to memory slot by slot, every one of the Rs values would
+// be a partial write of the same 64-byte block.)
+// The lane number, computed where it is used: the park address is a function of the lane alone, and a value the compiler
+// can derive outside the chain's loops it does derive there and keeps -- at 256 registers, spills -- across them.
+__device__ __forceinline__ unsigned wc_lane_here() {
+  unsigned l;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=&v"(l));
+  return l;
+}
+// bits[l] | bits[l ^ 16] | bits[l ^ 32] | bits[l ^ 48]: the OR over the four lanes q of a frame (as sum_rows4, common.h)
+__device__ __forceinline__ unsigned wc_or_rows4(unsigned a) {
+  auto r = __builtin_amdgcn_permlane16_swap(a, opaque_copy(a), false, false);
+  unsigned x = r[0], y = r[1];
+  asm volatile("" : "+v"(x), "+v"(y));
+  a = x | y;
+  auto r2 = __builtin_amdgcn_permlane32_swap(a, opaque_copy(a), false, false);
+  x = r2[0]; y = r2[1];
+  asm volatile("" : "+v"(x), "+v"(y));
+  return x | y;
+}
+// area: the wavefront's area (uniform).  The odd bin of frame c for `slot` is in lane (q = 0, c), as stored bits `bits`.
+// All four lanes of the frame write it (the same value to the same address): a write under a lane mask splits the last
+// tile's epilogue into basic blocks, and the register allocator then spills 35 registers across the whole evaluation.
+template <typename store_t>
+__device__ __forceinline__ void wc_park(char* area, unsigned xb, int slot, unsigned bits) {
+  const unsigned l = wc_lane_here();
+  const unsigned v = wc_or_rows4(l < 16u ? bits : 0u);
+  char* dst = area + (l & 15u) * xb + (unsigned)slot * (unsigned)sizeof(store_t);
+  if constexpr (sizeof(store_t) == 4) *reinterpret_cast<unsigned*>(dst) = v;
+  else *reinterpret_cast<unsigned short*>(dst) = (unsigned short)v;
+}
+template <typename store_t>
+__device__ __forceinline__ void wc_flush_odd(const WcArgs& a, __amdgpu_buffer_rsrc_t vrs, const char* area, bool fvalid, int nrow) {
+  __builtin_amdgcn_s_waitcnt(0xC07F);                     // lgkmcnt(0): the parked values are in LDS (gfx9 encoding)
+  __builtin_amdgcn_wave_barrier();
+  const unsigned xb = a.lay.xframe * (unsigned)sizeof(store_t);         // bytes of a frame's block, a multiple of 64
+  const unsigned l = wc_lane_here(), q = l >> 4;
+  const char* park = area + (l & 15u) * xb;
+  const unsigned xo = fvalid ? ((unsigned)a.lay.xbase + (unsigned)nrow * a.lay.xframe) * (unsigned)sizeof(store_t) : WC_OOB;
+  for (unsigned j = 16u * (unsigned)q; j < xb; j += 64u)
+    __builtin_amdgcn_raw_buffer_store_b128(*reinterpret_cast<const u32x4*>(park + j), vrs, xo + j, 0, 0);
+  __builtin_amdgcn_wave_barrier();                        // (the next wave tile parks into the same area)
+}
+
 // MAXT : compile-time bound of the bin tiles; EXACT: NT3 == MAXT (no per-tile checks)
 // LOL  : the lo fragments of W3 are in LDS too (bf16x3 mode, small F); otherwise they stream from L2
 // HIALL: every hi fragment of W3 is in LDS
@@ -214,8 +264,12 @@ __device__ __forceinline__ void wc_store_z(const WcArgs& a, const WcRes& R, cons
 // M2   : per-frame layer-1 bias B1 = b1 + W1[:, L:] y_n, else b1 from LDS.  At 4 wavefronts (512 registers each) the
 //        lane's 32 values stay in registers; at 8 (bf16 mode, 256 registers) each lane parks them as bf16 in a private
 //        8 x 8 bytes of LDS (4 KB per wavefront) and reads one 8-byte word back per layer-1 tile
-template <int MAXT, bool EXACT, bool SPLIT, bool STORE, int NWAVES, bool LOL, bool HIALL, bool M2, int GT>
+// ALN  : line-aligned store layout (STORE, F = 257: MAXT = 17, EXACT), see wc_flush_odd.  (Not at F = 513: the weights leave
+//        512 bytes of LDS, and a fifth bin tile streamed from L2 to make room costs registers this kernel does not have --
+//        20 to 144 bytes of scratch; those batches keep the padded layout, vn_wchain_park_fits.)
+template <int MAXT, bool EXACT, bool SPLIT, bool STORE, int NWAVES, bool LOL, bool HIALL, bool M2, int GT, bool ALN = false>
 __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const WcArgs a) {
+  static_assert(!ALN || (STORE && EXACT && MAXT == 17), "ALN");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   using L = WcLds<SPLIT>;
   constexpr int PARTS = L::PARTS;
@@ -251,6 +305,9 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
     float* b3s = reinterpret_cast<float*>(smem + L::B3);
     for (int i = threadIdx.x; i < HID; i += nthr) { b1s[i] = a.b1[i]; b2s[i] = a.b2[i]; }
     for (int i = threadIdx.x; i < 16 * NT3; i += nthr) b3s[i] = a.b3[i];
+    if (ALN)                                               // (the blocks' padding goes to the store as zeros)
+      for (unsigned e = threadIdx.x * 16u; e < NWAVES * WT_FRAMES * a.lay.xframe * (unsigned)sizeof(store_t); e += nthr * 16u)
+        *reinterpret_cast<u32x4*>(smem + a.park_lds + e) = u32x4{0u, 0u, 0u, 0u};
   }
   __syncthreads();
 
@@ -311,7 +368,10 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
     // ---- sample-variance store: slot r of the frame holds the variances of the proposal of post-burn-in step r,
     // slot R the state the chain is in when the burn-in ends; src[r][frame] names the slot of the state after
     // step r (mcem.py:429-437; the slot of a pass: vn_chain_pass, common.h)
-    const unsigned fbase = STORE ? (fr.fvalid ? (unsigned)nrow * (unsigned)(a.Rs * a.Fs) * (unsigned)sizeof(store_t) : WC_OOB) : 0u;
+    const unsigned fbase = STORE ? (fr.fvalid ? (unsigned)nrow * a.lay.frame * (unsigned)sizeof(store_t) : WC_OOB) : 0u;
+    // ALN: the wavefront's area of parked odd bins, [16 frames][xpark bytes]
+    const unsigned xpark = a.lay.xframe * (unsigned)sizeof(store_t);
+    char* const park = smem + (ALN ? a.park_lds + wave * WT_FRAMES * (int)xpark : 0);
     const unsigned zs_off = fr.fvalid ? ((unsigned)nrow * (unsigned)a.Rcap * LAT + 4u * q) * 4u : WC_OOB;      // Zs[nrow][r][4q..]
     const unsigned fr_off = (fr.fvalid && q == 0) ? (unsigned)nrow * 4u : WC_OOB;                                  // [step][nrow] tables
     const unsigned rp_off = ((unsigned)nrow * LAT + 4u * q) * 4u;                                               // eps[step][nrow][4q..]
@@ -338,7 +398,7 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
       // 7.2 leaves out the wait states a store of more than 8 bytes needs before its data registers are rewritten when
       // the scalar offset is a register (GCNHazardRecognizer assumes no hazard then; gfx950 has it: sporadic garbage
       // in the first dword of the 16-byte stores).
-      const unsigned voff = DOST ? fbase + (unsigned)slot * (unsigned)a.Fs * (unsigned)sizeof(store_t) : 0u;
+      const unsigned voff = DOST ? fbase + (unsigned)slot * a.lay.row * (unsigned)sizeof(store_t) : 0u;
       // B fragments of a layer's input: k-step s <-> feature tiles 2s (elements 0..3) and 2s+1 (elements 4..7)
       u32x4 bh[NK_H], bl[NK_H], ch[NK_H], cl[NK_H];
       auto put = [&](u32x4 (&dh)[NK_H], u32x4 (&dl)[NK_H], int t, const f32x4 h) {      // tile t of the next layer's input
@@ -502,7 +562,9 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
                     const f32x2 rc = {fast_rcp(pp[0]), fast_rcp(pp[1])};
                     px2 = (x2[t].lo * v1 + x2[t].hi * v0) * rc + px2;
                   }
-                  if (DOST) {
+                  if (DOST && ALN && t == MAXT - 1) {
+                    wc_park<store_t>(park, xpark, slot, SPLIT ? __builtin_bit_cast(unsigned, ev[0]) : (pk2(ev[0], ev[1]) & 0xFFFFu));
+                  } else if (DOST) {
                     if (SPLIT) {
                       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, ev), R.vrs, voff + 16u * q + 64u * t, 0, WC_ST_AUX);
                     } else {
@@ -599,6 +661,7 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
       WC_STAMP(4);
     }
     WC_STAMP_FLUSH;
+    if (ALN) wc_flush_odd<store_t>(a, R.vrs, park, fr.fvalid, nrow);
     wc_store_z(a, R, fr, rp_off, z);
   }
 }
@@ -616,8 +679,9 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES / 4) void wchain_kernel(const W
 // result -- are bit-identical to wchain_kernel's (tested).  Three workgroup barriers per evaluation.  A lone wavefront per
 // SIMD needed 7 450 cycles per evaluation for the whole decoder.
 // ---------------------------------------------------------------------------------------------------------------
-template <int MAXT, bool STORE, bool M2>
+template <int MAXT, bool STORE, bool M2, bool ALN = false>
 __global__ __launch_bounds__(256, 1) void wchain4_kernel(const WcArgs a) {
+  static_assert(!ALN || STORE, "ALN");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int NP = (MAXT - 1) / 2;                     // bin-tile pairs (8 / 16); tile MAXT-1 is the odd last one
   constexpr int PPW = NP / 4, NOWN = 2 * PPW + 1;        // pairs and tiles per wavefront (wavefront 0 owns the last tile too)
@@ -663,6 +727,12 @@ __global__ __launch_bounds__(256, 1) void wchain4_kernel(const WcArgs a) {
   }
 
   const WcRes R = wc_resources<STORE, M2>(a);
+  // ALN: wavefront 0 owns the last bin tile and with it the area of parked odd bins (wc_flush_odd)
+  char* const park = smem + (ALN ? a.park_lds : 0);
+  const unsigned xpark = a.lay.xframe * 2u;
+  if (ALN && wave == 0)
+    for (unsigned e = (unsigned)lane * 16u; e < WT_FRAMES * a.lay.xframe * 2u; e += 1024u)
+      *reinterpret_cast<u32x4*>(smem + a.park_lds + e) = u32x4{0u, 0u, 0u, 0u};
 
   for (int wt = blockIdx.x; wt < a.n_wtiles; wt += (int)gridDim.x) {
     const WcFrame fr = wc_frame(a, wt, c, wave == 0);
@@ -697,7 +767,7 @@ __global__ __launch_bounds__(256, 1) void wchain4_kernel(const WcArgs a) {
     float z[8];
     wc_load_z(R, fr, q, z);
     // rows: every wavefront writes its own tiles' part; samples, slot map, acceptances and Z: wavefront 0 alone
-    const unsigned fbase = STORE ? (fr.fvalid ? (unsigned)nrow * (unsigned)(a.Rs * a.Fs) * 2u : WC_OOB) : 0u;
+    const unsigned fbase = STORE ? (fr.fvalid ? (unsigned)nrow * a.lay.frame * 2u : WC_OOB) : 0u;
     const unsigned zs_off = fr.keeps ? ((unsigned)nrow * (unsigned)a.Rcap * LAT + 4u * q) * 4u : WC_OOB;
     const unsigned fr_off = (fr.keeps && q == 0) ? (unsigned)nrow * 4u : WC_OOB;
     const unsigned rp_off = ((unsigned)nrow * LAT + 4u * q) * 4u;
@@ -711,7 +781,7 @@ __global__ __launch_bounds__(256, 1) void wchain4_kernel(const WcArgs a) {
 
     auto energy = [&](const float (&zz)[8], int slot, auto dost) -> double {
       constexpr bool DOST = STORE && decltype(dost)::value;
-      const unsigned voff = DOST ? fbase + (unsigned)slot * (unsigned)a.Fs * 2u : 0u;
+      const unsigned voff = DOST ? fbase + (unsigned)slot * a.lay.row * 2u : 0u;
       u32x4 bh[NK_H], ch[NK_H];
       // hidden layers: this wavefront computes feature tiles 2w, 2w+1 -- after tanh and the bf16 rounding exactly k-step w of
       // the next layer's input fragments (file header) -- and the four k-steps are exchanged through LDS
@@ -778,6 +848,8 @@ __global__ __launch_bounds__(256, 1) void wchain4_kernel(const WcArgs a) {
           if (i < 2 * PPW) {
             if ((i & 1) == 0) { pk_even0 = p0; pk_even1 = p1; }
             else __builtin_amdgcn_raw_buffer_store_b128(u32x4{pk_even0, pk_even1, p0, p1}, R.vrs, voff + 16u * q + 64u * (t >> 1), 0, WC_ST_AUX);
+          } else if (ALN) {
+            wc_park<__bf16>(park, xpark, slot, p0 & 0xFFFFu);
           } else {
             __builtin_amdgcn_raw_buffer_store_b64(u32x2{p0, p1}, R.vrs, voff + 8u * q + 32u * t, 0, WC_ST_AUX);
           }
@@ -868,6 +940,7 @@ __global__ __launch_bounds__(256, 1) void wchain4_kernel(const WcArgs a) {
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{z[4], z[5], z[6], z[7]}), R.zs_rs, zo + 64u, 0, 0);
       }
     }
+    if (ALN && wave == 0) wc_flush_odd<__bf16>(a, R.vrs, park, fr.fvalid, nrow);
     wc_store_z(a, R, fr, rp_off, z);
   }
 }
@@ -885,6 +958,25 @@ int wc_by_m2_store(const WcArgs& a, Go&& go) {
   if (a.B1) return a.VsS ? go(std::true_type{}, std::true_type{}) : go(std::true_type{}, std::false_type{});
   return a.VsS ? go(std::false_type{}, std::true_type{}) : go(std::false_type{}, std::false_type{});
 }
+constexpr int WC_GT33 = 4;                         // F = 513: bin tiles whose fragments stay in global memory
+
+// LDS of wchain_kernel for this plan: weights and biases, the M2 stash of layer-1 bias rows (8 wavefronts), and with the
+// line-aligned store layout (xframe_bytes > 0: bytes of a frame's block of odd bins) one area of 16 blocks per wavefront
+struct WcLdsPlan { int nwaves; bool lol; size_t b1_lds, park_lds, total; };
+WcLdsPlan wc_lds_plan(const vaenmf_plan* p, bool m2, size_t xframe_bytes) {
+  const bool split = p->cfg.precision == VAENMF_PREC_BF16X3;
+  WcLdsPlan l;
+  const size_t fixed = split ? WcLds<true>::fixed_bytes : WcLds<false>::fixed_bytes;
+  const int gt = p->NT3c == 33 ? WC_GT33 : 0;
+  const size_t w3hi = (size_t)(p->NT3c - gt) * NK_H * 1024;
+  l.lol = split && p->NT3c <= 5;                        // bf16x3: the lo fragments of W3 fit in LDS up to 5 tiles (F <= 80), else they stream from L2
+  l.nwaves = (split || p->NT3c == 33) ? 4 : 8;
+  l.b1_lds = fixed + w3hi * (l.lol ? 2 : 1);
+  l.park_lds = l.b1_lds + ((m2 && l.nwaves == 8) ? (size_t)l.nwaves * NT_H * 512 : 0);
+  l.total = l.park_lds + (size_t)l.nwaves * WT_FRAMES * xframe_bytes;
+  return l;
+}
+
 // M1 runs NW1 wavefronts per workgroup; M2 the same (at 8 the per-frame layer-1 bias rows live in LDS: b1_lds)
 template <int MAXT, bool EXACT, bool SPLIT, int NW1, bool LOL, int GT = 0>
 int wc_launch_s(const WcArgs& a, int nwt, int n_sms, size_t lds, hipStream_t st) {
@@ -893,17 +985,30 @@ int wc_launch_s(const WcArgs& a, int nwt, int n_sms, size_t lds, hipStream_t st)
   const int cap = vn_switches().grid_cap;               // (tests: a small grid makes every wavefront walk several wave tiles)
   if (cap > 0 && cap < grid) grid = cap;
   return wc_by_m2_store(a, [&](auto m2, auto store) -> int {
-    auto* fn = wchain_kernel<MAXT, EXACT, SPLIT, decltype(store)::value, NW1, LOL, true, decltype(m2)::value, GT>;
-    if (int e = vn_ensure_dyn_lds((const void*)fn, VN_LDS_LIMIT)) return e;
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(NW1 * 64), lds, st, a);
-    return 0;
+    auto go = [&](auto* fn) -> int {
+      if (int e = vn_ensure_dyn_lds((const void*)fn, VN_LDS_LIMIT)) return e;
+      hipLaunchKernelGGL(fn, dim3(grid), dim3(NW1 * 64), lds, st, a);
+      return 0;
+    };
+    if constexpr (decltype(store)::value && EXACT && MAXT == 17) {      // the line-aligned store layout (F = 257)
+      if (a.lay.aligned) return go(wchain_kernel<MAXT, EXACT, SPLIT, true, NW1, LOL, true, decltype(m2)::value, GT, true>);
+    }
+    return go(wchain_kernel<MAXT, EXACT, SPLIT, decltype(store)::value, NW1, LOL, true, decltype(m2)::value, GT>);
   });
 }
 // four wavefronts per wave tile: one workgroup per tile, exchange areas only in LDS
 template <int MAXT>
-int wc_launch4(const WcArgs& a, hipStream_t st) {
+int wc_launch4(WcArgs a, hipStream_t st) {
   const size_t lds4 = 2 * 4 * 64 * 16 + 20 * 64 * 4;
   return wc_by_m2_store(a, [&](auto m2, auto store) -> int {
+    if constexpr (decltype(store)::value) {
+      if (a.lay.aligned) {                                // wavefront 0's area of parked odd bins behind the exchange areas
+        a.park_lds = (int)lds4;
+        hipLaunchKernelGGL((wchain4_kernel<MAXT, true, decltype(m2)::value, true>), dim3(a.n_wtiles), dim3(256),
+                           lds4 + (size_t)WT_FRAMES * a.lay.xframe * 2, st, a);
+        return 0;
+      }
+    }
     hipLaunchKernelGGL((wchain4_kernel<MAXT, decltype(store)::value, decltype(m2)::value>), dim3(a.n_wtiles), dim3(256), lds4, st, a);
     return 0;
   });
@@ -934,6 +1039,21 @@ extern "C" int vaenmf_wchain_addressable(int64_t NT, int32_t Rcap, int32_t steps
   if (replay && nt * S * LAT * 4 >= lim) return 0;                     // eps
   return 1;
 }
+// small batches (at most one wave tile per CU) in bf16 mode at 17 / 33 bin tiles: four wavefronts per wave tile (wchain4_kernel)
+static bool wc_runs_wchain4(const vaenmf_plan* p) {
+  return p->cfg.precision != VAENMF_PREC_BF16X3 && (p->NT3c == 17 || p->NT3c == 33) && p->n_wtiles <= p->n_sms && vn_switches().wchain4;
+}
+// The line-aligned store layout needs LDS for the odd bins of Rs slots of 16 frames per wavefront.  wchain4_kernel has it;
+// beside wchain_kernel's weights there is room at F = 257 (bf16: any slot count for M1, up to 64 slots for M2; the float rows
+// of bf16x3: up to 32 slots) and none at F = 513.
+bool vn_wchain_park_fits(const vaenmf_plan* p, int Rs, bool m2) {
+  if (p->NT3c != 17 && p->NT3c != 33) return true;       // (no aligned layout for these F)
+  if (wc_runs_wchain4(p)) return true;
+  if (p->NT3c == 33) return false;
+  const int esz = p->cfg.precision == VAENMF_PREC_BF16X3 ? 4 : 2;
+  const size_t xb = ((size_t)Rs * esz + 63) / 64 * 64;
+  return wc_lds_plan(p, m2, xb).total <= (size_t)VN_LDS_LIMIT;
+}
 bool vn_wchain_fits(const vaenmf_plan* p, const VnChainCall& cc) {
   return vaenmf_wchain_addressable(p->NT, cc.Rcap, cc.nsamples + cc.burnin, p->Fs, p->Kp, p->n_utt, cc.eps != nullptr) != 0;
 }
@@ -946,29 +1066,28 @@ int vn_launch_wchain(vaenmf_plan* p, const VnChainCall& cc, hipStream_t st) {
   a.NT3 = p->NT3c; a.Tm = split ? 0 : ((p->NT3c - 1) & ~1); a.F = p->cfg.F; a.Fs = p->Fs;
   a.X2 = cc.X2; a.W = cc.W; a.Ht = cc.Ht; a.g = cc.g; a.B1 = cc.B1; a.Vb = p->Vb_ext;
   a.Z = cc.Z; a.Zs = cc.Zs; a.acc_out = cc.acc_out;
-  a.VsS = cc.VsS; a.VsS_bytes = (unsigned)cc.VsS_bytes; a.src = cc.src; a.Rs = cc.Rs;
+  a.VsS = cc.VsS; a.VsS_bytes = (unsigned)cc.VsS_bytes; a.src = cc.src; a.Rs = cc.Rs; a.lay = cc.lay;
   a.wt_utt = p->d_wt_utt; a.wt_n0 = p->d_wt_n0; a.wt_cnt = p->d_wt_cnt; a.n_wtiles = p->n_wtiles;
   a.frame_off = p->d_frame_off; a.utt_seed = p->d_utt_seed; a.eps = cc.eps; a.u = cc.u;
   a.Kp = p->Kp; a.NT = p->NT; a.n_utts = p->n_utt; a.Rcap = cc.Rcap; a.nsamples = cc.nsamples; a.burnin = cc.burnin;
   a.rng_mode = cc.rng_mode; a.update_Z = cc.update_Z; a.call = cc.call; a.sd = cc.sd; a.sd_hi = cc.sd_hi; a.one_hidden = cc.one_hidden;
   a.n_hi_lds = p->NT3c;
-  const size_t fixed = split ? WcLds<true>::fixed_bytes : WcLds<false>::fixed_bytes;
-  constexpr int GT33 = 4;                                // F = 513: bin tiles whose fragments stay in global memory
-  const size_t w3hi = (size_t)(p->NT3c == 33 ? p->NT3c - GT33 : p->NT3c) * NK_H * 1024;
-  const bool lol = split && p->NT3c <= 5;              // bf16x3: the lo fragments of W3 fit in LDS up to 5 tiles (F <= 80), else they stream from L2
+  constexpr int GT33 = WC_GT33;
   constexpr int NW_BF16 = 8, NW_X3 = 4;
-  const int nwaves = (split || p->NT3c == 33) ? 4 : NW_BF16;
-  a.b1_lds = (int)(fixed + w3hi * (lol ? 2 : 1));
-  const size_t lds = (size_t)a.b1_lds + ((cc.B1 && nwaves == 8) ? (size_t)nwaves * NT_H * 512 : 0);
-  VN_REQUIRE(lds <= (size_t)VN_LDS_LIMIT, "wave chain: %zu bytes of LDS needed", lds);
-  // small batches (at most one wave tile per CU) in bf16 mode at 17 / 33 bin tiles: four wavefronts per wave tile (wchain4_kernel)
-  if (!split && (p->NT3c == 17 || p->NT3c == 33) && p->n_wtiles <= p->n_sms && vn_switches().wchain4) {
+  if (wc_runs_wchain4(p)) {                            // (its LDS: exchange areas and, line-aligned store, one area of odd bins -- wc_launch4)
     const int rc4 = p->NT3c == 17 ? wc_launch4<17>(a, st) : wc_launch4<33>(a, st);
     if (rc4) return rc4;
     VN_CHECK_HIP(hipGetLastError());
     p->last_chain_kernel = 2;
     return 0;
   }
+  const bool aln = cc.VsS && cc.lay.aligned;
+  const WcLdsPlan lp = wc_lds_plan(p, cc.B1 != nullptr, aln ? (size_t)cc.lay.xframe * (split ? 4 : 2) : 0);
+  a.b1_lds = (int)lp.b1_lds;
+  a.park_lds = (int)lp.park_lds;
+  const size_t lds = lp.total;
+  VN_REQUIRE(lds <= (size_t)VN_LDS_LIMIT, "wave chain: %zu bytes of LDS needed", lds);
+  VN_REQUIRE(!aln || p->NT3c == 17, "wave chain: no line-aligned store layout at %d bin tiles", p->NT3c);
   // wavefronts per workgroup: 8 (two per SIMD, 256 registers each) in bf16 mode, 4 (512 registers) in bf16x3 mode
   int rc;
   if (p->NT3c == 33)     rc = wc_launch_s<33, true, false, 4, false, GT33>(a, p->n_wtiles, p->n_sms, lds, st);

@@ -58,6 +58,40 @@ struct VnEmGraphs {
   void release();                                                       // vaenmf_plan_destroy
 };
 
+// Where the sample-variance store keeps the row of (frame n, slot s) and its odd last bin F-1, in ELEMENTS of the store's
+// type (bf16, or float in bf16x3 mode); every writer and reader of the store takes its addresses from here:
+//   bins 0 .. of the row : n * frame + s * row
+//   bin F-1              : xbase + n * xframe + s * xslot
+// Padded layout (every F): a row is Fs elements with bin F-1 inside it (row = xslot = Fs, frame = xframe = Rs Fs,
+// xbase = F-1).  F = 257 in bf16 is 544 B per row: every odd slot starts 32 B off a 64-byte block and every row shares
+// its first and last cache line with its neighbours.
+// Line-aligned layout (F = 256 c + 1, VAENMF_STORE_ALIGNED): a row is bins 0 .. 256 c - 1 and nothing else (512 c or
+// 1024 c bytes), so every row starts on a 128-byte line and covers whole lines; bin F-1 of a frame's Rs slots is one
+// contiguous block of Rs elements padded to 64 B, the blocks in a region of their own behind the rows of all frames.
+struct VnStoreLayout {
+  uint32_t row, frame;       // slot to slot, frame to frame
+  uint32_t xslot, xframe;    // the same for bin F-1
+  uint64_t xbase;            // bin F-1 of frame 0, slot 0
+  int32_t aligned;           // 1: the line-aligned layout
+};
+// frames: frame blocks of the store (vaenmf_mh_chain: NT + 1, a spare block for lanes without a frame); esz: 2 or 4
+inline VnStoreLayout vn_store_layout_of(int F, int Fs, int esz, int Rs, size_t frames, bool aligned) {
+  VnStoreLayout l;
+  if (aligned && (F == 257 || F == 513)) {
+    l.row = (uint32_t)(F - 1); l.frame = (uint32_t)Rs * l.row;
+    l.xslot = 1; l.xframe = (uint32_t)(((size_t)Rs * esz + 63) / 64 * 64 / esz);
+    l.xbase = (uint64_t)frames * l.frame; l.aligned = 1;
+  } else {
+    l.row = l.xslot = (uint32_t)Fs; l.frame = l.xframe = (uint32_t)Rs * (uint32_t)Fs;
+    l.xbase = (uint64_t)(F - 1); l.aligned = 0;
+  }
+  return l;
+}
+// bytes of a store of `frames` frame blocks (both regions)
+inline size_t vn_store_bytes(const VnStoreLayout& l, size_t frames, int esz) {
+  return (l.aligned ? frames * ((size_t)l.frame + l.xframe) : frames * (size_t)l.frame) * esz;
+}
+
 struct vaenmf_plan {
   vaenmf_config cfg;
   int Fs, Kp, NT3;           // padded bins, padded rank, feature tiles of 16 on the MFMA path of the last layer
@@ -109,10 +143,11 @@ struct vaenmf_plan {
   double* cost_frames;       // [VN_COST_CHUNK][max_frames] per-frame cost sums of the fused driver (a row per iteration of a chunk)
   // sample-variance store (vaenmf_sample_store): the MH chain keeps the decoded variances of its samples here
   bool store_on;
-  void* VsS;                 // [NT][store_Rs][Fs], float (bf16x3 mode) or bf16 (bf16 mode)
+  void* VsS;                 // [NT + 1] frame blocks of store_Rs rows, float (bf16x3 mode) or bf16 (bf16 mode), laid out as store_lay
   int32_t* src;              // [NT][store_Rs]
   size_t VsS_cap, src_cap;   // allocated bytes / elements
   int store_R, store_Rs;     // samples / slots per frame of the last chain that filled the store (0: empty)
+  VnStoreLayout store_lay;   // ... and the layout it wrote them in
   int n_sms;
   // optional per-kernel timing with HIP events on the launch stream (vaenmf_profile_*)
   bool prof_on;
@@ -135,6 +170,7 @@ struct VnChainCall {
   float *Z, *Zs, *acc_out;
   const float *eps, *u;
   void* VsS; size_t VsS_bytes; int32_t* src; int Rs;
+  VnStoreLayout lay;         // of the store for this call's Rs (vn_store_layout)
   int Rcap, nsamples, burnin, rng_mode, update_Z;
   uint32_t call;
   float sd;
@@ -153,6 +189,7 @@ struct VnSwitches {
   int grid_cap;        // VAENMF_GRID_CAP=n: at most n workgroups for the persistent kernels -- wchain_kernel, decode_kernel, the streaming
                        // kernels of stream.hip -- so that a small batch walks their tile / frame loops several times (tests; 0: no cap)
   bool keep_zs;        // VAENMF_KEEP_ZS=1: the E-step chains of the sample-store path record their samples anyway
+  bool store_aligned;  // VAENMF_STORE_ALIGNED=0: the padded store layout for every F (VnStoreLayout)
 };
 
 // ---- functions one source file defines and another calls (the file that defines each) ----
@@ -161,6 +198,8 @@ int vn_ensure_dyn_lds(const void* fn, int bytes);          // plan.hip: per-devi
 extern long long g_vn_dev_allocs;                          // plan.hip: device allocations made by the library (VAENMF_Q_DEV_ALLOCS)
 bool vn_wchain_supported(const vaenmf_plan* p);            // chain.hip
 bool vn_wchain_fits(const vaenmf_plan* p, const VnChainCall& cc);                 // chain.hip
+bool vn_wchain_park_fits(const vaenmf_plan* p, int Rs, bool m2);                  // chain.hip: LDS for the odd bins of Rs slots beside the weights
+VnStoreLayout vn_store_layout(const vaenmf_plan* p, int Rs, bool m2);             // driver.hip: the store's layout for chains of Rs slots (m2: with B1)
 int vn_launch_wchain(vaenmf_plan* p, const VnChainCall& cc, hipStream_t st);      // chain.hip: builds WcArgs, picks the kernel
 int vn_launch_tchain(vaenmf_plan* p, const VnChainCall& cc, hipStream_t st);      // engine.hip: builds ChainArgs, picks the geometry
 int vn_launch_widechain(vaenmf_plan* p, const VnChainCall& cc, hipStream_t st);   // wide.hip: the chain of a wide plan

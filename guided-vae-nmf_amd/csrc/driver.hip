@@ -5,6 +5,23 @@
 #include "common.h"
 #include <cstring>
 
+// The layout the chains of Rs slots write the store in and its readers read it in (VnStoreLayout, common.h): line-aligned
+// for F = 257 / 513 unless VAENMF_STORE_ALIGNED=0 -- or unless the wave-private chain kernels, which collect a frame's odd
+// bins in LDS, have no room for Rs of them beside their weights (vn_wchain_park_fits)
+VnStoreLayout vn_store_layout(const vaenmf_plan* p, int Rs, bool m2) {
+  const int esz = p->cfg.precision == VAENMF_PREC_BF16X3 ? 4 : 2;
+  bool aligned = vn_switches().store_aligned;
+  if (aligned && !p->wide && vn_wchain_supported(p) && !vn_wchain_park_fits(p, Rs, m2)) aligned = false;
+  return vn_store_layout_of(p->cfg.F, p->Fs, esz, Rs, (size_t)(p->NT > 0 ? p->NT : p->cfg.max_frames) + 1, aligned);
+}
+extern "C" int vaenmf_store_layout(int32_t F, int32_t Fs, int32_t elt_bytes, int32_t Rs, int64_t frames, int32_t aligned, int64_t* out7) {
+  VN_REQUIRE(out7 != nullptr && F >= 1 && Fs >= F && (elt_bytes == 2 || elt_bytes == 4) && Rs >= 1 && frames >= 1, "vaenmf_store_layout: bad arguments");
+  const VnStoreLayout l = vn_store_layout_of(F, Fs, elt_bytes, Rs, (size_t)frames, aligned != 0);
+  out7[0] = l.row; out7[1] = l.frame; out7[2] = l.xslot; out7[3] = l.xframe; out7[4] = (int64_t)l.xbase; out7[5] = l.aligned;
+  out7[6] = (int64_t)vn_store_bytes(l, (size_t)frames, elt_bytes);
+  return 0;
+}
+
 extern "C" int vaenmf_mh_chain(vaenmf_plan* p, const float* X2, const float* W, const float* Ht, const float* g,
                                float* Z, int32_t update_Z, const float* B1, float* Zs, int32_t Rcap, int32_t nsamples,
                                int32_t burnin, float var_rw, const vaenmf_rng* rng, float* acc_out, void* stream) {
@@ -22,13 +39,13 @@ extern "C" int vaenmf_mh_chain(vaenmf_plan* p, const float* X2, const float* W, 
   p->store_R = p->store_Rs = 0;
   if (p->store_on) {                                    // sample-variance store: sized by vaenmf_sample_store, never here
     const int Rs = nsamples + 1;
-    const size_t esz = split ? sizeof(float) : sizeof(__bf16);
-    const size_t need_v = (size_t)(p->NT + 1) * Rs * p->Fs * esz, need_s = (size_t)p->NT * Rs;   // + a spare block (idle lanes)
+    const VnStoreLayout lay = vn_store_layout(p, Rs, B1 != nullptr);
+    const size_t need_v = vn_store_bytes(lay, (size_t)p->NT + 1, split ? 4 : 2), need_s = (size_t)p->NT * Rs;   // + a spare block (idle lanes); rows and odd bins
     VN_REQUIRE(need_v < 0xE0000000ull, "sample store: %d frames x %d slots x %d bins exceeds the 32-bit byte offsets of "
                "the chain kernel; bind a smaller batch or switch the store off", p->NT, Rs, p->Fs);
     VN_REQUIRE(need_v <= p->VsS_cap && need_s <= p->src_cap, "sample store too small for %d frames x %d samples: call "
                "vaenmf_sample_store(plan, max_samples) after vaenmf_bind_batch (no allocation happens in vaenmf_mh_chain)", p->NT, nsamples);
-    cc.VsS = p->VsS; cc.VsS_bytes = need_v; cc.src = p->src; cc.Rs = Rs;
+    cc.VsS = p->VsS; cc.VsS_bytes = need_v; cc.src = p->src; cc.Rs = Rs; cc.lay = lay;
   }
   // wide decoder shapes: one kernel for every batch (wide.hip, 64-bit addresses).  Else wave-private chains (chain.hip)
   // while every buffer of the batch is within their 32-bit byte offsets; a larger batch (about 300 k frames at 105
@@ -39,7 +56,7 @@ extern "C" int vaenmf_mh_chain(vaenmf_plan* p, const float* X2, const float* W, 
     ProfScope ps(p, VN_K_CHAIN, st);
     if (int e = p->wide ? vn_launch_widechain(p, cc, st) : use_wchain ? vn_launch_wchain(p, cc, st) : vn_launch_tchain(p, cc, st)) return e;
   }
-  if (p->store_on) { p->store_R = nsamples; p->store_Rs = nsamples + 1; }
+  if (p->store_on) { p->store_R = nsamples; p->store_Rs = nsamples + 1; p->store_lay = cc.lay; }
   return 0;
 }
 
@@ -54,7 +71,10 @@ extern "C" int vaenmf_sample_store(vaenmf_plan* p, int32_t max_samples) {
   const size_t esz = p->cfg.precision == VAENMF_PREC_BF16X3 ? sizeof(float) : sizeof(__bf16);
   // sized for the bound batch (or, before a batch is bound, for the plan's frame capacity)
   const size_t frames = (size_t)(p->NT > 0 ? p->NT : p->cfg.max_frames) + 1, Rs = (size_t)max_samples + 1;
-  size_t need_v = frames * Rs * p->Fs * esz, need_s = frames * Rs;
+  // (both layouts: VAENMF_STORE_ALIGNED is read at every chain call)
+  const size_t need_pad = vn_store_bytes(vn_store_layout_of(p->cfg.F, p->Fs, (int)esz, (int)Rs, frames, false), frames, (int)esz);
+  const size_t need_aln = vn_store_bytes(vn_store_layout_of(p->cfg.F, p->Fs, (int)esz, (int)Rs, frames, true), frames, (int)esz);
+  size_t need_v = need_pad > need_aln ? need_pad : need_aln, need_s = frames * Rs;
   if (need_v >= 0xE0000000ull) need_v = 0xE0000000ull - 16;    // larger batches fall back to decoding (vaenmf_em_run); offsets from 0xF0000000 mark idle lanes
   if (need_v > p->VsS_cap) {
     if (p->VsS) VN_CHECK_HIP(hipFree(p->VsS));
@@ -75,12 +95,16 @@ extern "C" int vaenmf_sample_store(vaenmf_plan* p, int32_t max_samples) {
 }
 
 namespace {
+// (line-aligned layout: the row's bins, bin F-1 from the frame's block of odd bins, zeros in the padding)
 template <typename ST>
-__global__ void store_gather_kernel(const ST* __restrict__ VsS, const int32_t* __restrict__ src, int NT, int R, int Rs, int Fs,
+__global__ void store_gather_kernel(const ST* __restrict__ VsS, const int32_t* __restrict__ src, int NT, int R, VnStoreLayout lay, int F, int Fs,
                                     float* __restrict__ out) {
   const int n = blockIdx.x / R, r = blockIdx.x - n * R;
-  const ST* row = VsS + ((size_t)n * Rs + src[(size_t)r * NT + n]) * Fs;
-  for (int f = threadIdx.x; f < Fs; f += blockDim.x) out[((size_t)n * R + r) * Fs + f] = (float)row[f];
+  const int sl = src[(size_t)r * NT + n];
+  const ST* row = VsS + (size_t)n * lay.frame + (size_t)sl * lay.row;
+  const ST* xp = VsS + lay.xbase + (size_t)n * lay.xframe + (size_t)sl * lay.xslot;
+  for (int f = threadIdx.x; f < Fs; f += blockDim.x)
+    out[((size_t)n * R + r) * Fs + f] = f < (int)lay.row ? (float)row[f] : (f == F - 1 ? (float)*xp : 0.f);
 }
 }  // namespace
 
@@ -89,10 +113,10 @@ extern "C" int vaenmf_sample_store_gather(vaenmf_plan* p, float* Vs_out, void* s
   VN_REQUIRE(Vs_out != nullptr, "null output");
   if (p->cfg.precision == VAENMF_PREC_BF16X3)
     hipLaunchKernelGGL(store_gather_kernel<float>, dim3((unsigned)(p->NT * p->store_R)), dim3(64), 0, (hipStream_t)stream,
-                       reinterpret_cast<const float*>(p->VsS), p->src, p->NT, p->store_R, p->store_Rs, p->Fs, Vs_out);
+                       reinterpret_cast<const float*>(p->VsS), p->src, p->NT, p->store_R, p->store_lay, p->cfg.F, p->Fs, Vs_out);
   else
     hipLaunchKernelGGL(store_gather_kernel<__bf16>, dim3((unsigned)(p->NT * p->store_R)), dim3(64), 0, (hipStream_t)stream,
-                       reinterpret_cast<const __bf16*>(p->VsS), p->src, p->NT, p->store_R, p->store_Rs, p->Fs, Vs_out);
+                       reinterpret_cast<const __bf16*>(p->VsS), p->src, p->NT, p->store_R, p->store_lay, p->cfg.F, p->Fs, Vs_out);
   VN_CHECK_HIP(hipGetLastError());
   return 0;
 }
@@ -133,7 +157,7 @@ VnEmGraphs::Key em_graph_key(const vaenmf_plan* p, const EmCall& c, bool stored,
       (uint64_t)p->cfg.precision, (uint64_t)p->cfg.K, (uint64_t)p->cfg.F,
       (uint64_t)sw.wchain4, (uint64_t)sw.team_chain, (uint64_t)sw.wfused, (uint64_t)sw.wgroup, (uint64_t)(uint32_t)sw.wfused_grid,
       (uint64_t)(uint32_t)sw.grid_cap,
-      (uint64_t)sw.keep_zs};
+      (uint64_t)sw.keep_zs, (uint64_t)sw.store_aligned};
 }
 }  // namespace
 
@@ -202,7 +226,7 @@ static int em_run_body(vaenmf_plan* p, const EmCall& c, bool stored, void* strea
 static int em_graph_launch(vaenmf_plan* p, VnEmGraphs::Graph& gph, const EmCall& c, bool stored, hipStream_t st) {
   VN_CHECK_HIP(hipGraphLaunch(gph.exec, st));
   gph.used = ++p->graphs.tick;
-  if (stored) { p->store_R = c.nsWF; p->store_Rs = c.nsWF + 1; }
+  if (stored) { p->store_R = c.nsWF; p->store_Rs = c.nsWF + 1; p->store_lay = vn_store_layout(p, c.nsWF + 1, c.B1 != nullptr); }
   p->last_chain_kernel = gph.chain_kernel;
   p->last_w_fused = gph.w_fused;
   p->graphs.last = 1;
@@ -235,8 +259,8 @@ extern "C" int vaenmf_em_run(vaenmf_plan* p, const float* X2, float* W, float* H
   // M-step / Wiener filter stream them; otherwise they decode Zs again
   // (a batch too large for the store's 32-bit element offsets decodes; every F the plan accepts, <= 640, is in the streaming
   // kernels' bin range)
-  const size_t esz = p->cfg.precision == VAENMF_PREC_BF16X3 ? sizeof(float) : sizeof(__bf16);
-  auto fits = [&](int ns) { return (size_t)(p->NT + 1) * (ns + 1) * p->Fs * esz < 0xE0000000ull; };
+  const int esz = p->cfg.precision == VAENMF_PREC_BF16X3 ? 4 : 2;
+  auto fits = [&](int ns) { return vn_store_bytes(vn_store_layout(p, ns + 1, B1 != nullptr), (size_t)p->NT + 1, esz) < 0xE0000000ull; };
   const bool want = p->store_on, stored = want && fits(nsE) && fits(nsWF);
   // a wide plan has no decoding M-step / Wiener kernels to fall back to
   VN_REQUIRE(!p->wide || want, "vaenmf_em_run on a wide decoder plan streams the sample store: switch it on with vaenmf_sample_store first");

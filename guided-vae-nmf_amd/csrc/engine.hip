@@ -359,7 +359,8 @@ struct ChainArgs {
   const float *X2, *W, *Ht, *g, *B1;
   const float* Vb;           // external noise variance [NT][Fs] (the *_noNMF variants, mcem.py:493-760) or null: Vb = W H
   float *Z, *Zs, *acc_out;
-  void* VsS;                 // sample-variance store [NT][Rs][Fs] (float in bf16x3 mode, bf16 in bf16 mode) or null
+  void* VsS;                 // sample-variance store (float in bf16x3 mode, bf16 in bf16 mode), laid out as `lay`, or null
+  VnStoreLayout lay;         // (common.h)
   int32_t* src;              // [Rs][NT] (sample-major): slot of VsS that holds the variances of sample r of frame n
   int Rs;                    // slots per frame: nsamples + 1
   const int32_t *tile_utt, *tile_n0, *tile_cnt, *frame_off;
@@ -489,7 +490,7 @@ __global__ __launch_bounds__(NW * NTEAM * 64) void mh_chain_kernel(const ChainAr
   if (STORE) {
 #pragma unroll
     for (int fg = 0; fg < 2; ++fg)      // BYTE offset (the host keeps the store below 4 GB)
-      voff[fg] = ((uint32_t)(fvalid[fg] ? nrow[fg] : a.NT) * (uint32_t)(a.Rs * a.Fs) + 4u * q) * (uint32_t)sizeof(store_t);
+      voff[fg] = ((uint32_t)(fvalid[fg] ? nrow[fg] : a.NT) * a.lay.frame + 4u * q) * (uint32_t)sizeof(store_t);
   }
   // ---- noise streams: thread of the team <-> (frame of the team, latent quad); 256 streams
   const int sid = threadIdx.x - d.team * NW * 64, sfr = sid >> 3, squad = sid & 7;
@@ -530,7 +531,7 @@ __global__ __launch_bounds__(NW * NTEAM * 64) void mh_chain_kernel(const ChainAr
   auto energy = [&](const float (&zz)[2][8], double (&E)[2], int next_step, int slot, auto dost) {
     constexpr bool DOST = STORE && decltype(dost)::value;
     // uniform base (+ slot, SGPR) + 32-bit per-lane byte offset + the tile's constant: no 64-bit VALU address math
-    char* const vbase = reinterpret_cast<char*>(a.VsS) + (DOST ? (size_t)slot * a.Fs * sizeof(store_t) : 0);
+    char* const vbase = reinterpret_cast<char*>(a.VsS) + (DOST ? (size_t)slot * a.lay.row * sizeof(store_t) : 0);
     bf16x8 zhi[2], zlo[2];
     split8<SPLIT>(zz[0], zhi[0], zlo[0]);
     split8<SPLIT>(zz[1], zhi[1], zlo[1]);
@@ -580,6 +581,11 @@ __global__ __launch_bounds__(NW * NTEAM * 64) void mh_chain_kernel(const ChainAr
         const float vx = gn[fg] * vs + vbn[fg];
         const float term = fast_log(vx) + x2n[fg] * fast_rcp(vx);
         e[fg] += (w == 0 && q == 0) ? (double)term : 0.0;        // counted once per frame
+        if (DOST && w == 2 && q == 0 && a.lay.aligned) {
+          // line-aligned layout: the bin goes to the frame's block of odd bins (this kernel only has to be correct there: the
+          // wave-private chains, which run these shapes, write a frame's block once, in 16-byte pieces)
+          reinterpret_cast<store_t*>(a.VsS)[a.lay.xbase + (size_t)(fvalid[fg] ? nrow[fg] : a.NT) * a.lay.xframe + (size_t)slot * a.lay.xslot] = (store_t)vs;
+        } else
         if (DOST && w == 2 && q == 0) {      // (the per-step bookkeeping stores are spread over the waves of the team)
           // the whole 16-bin tail of the row (the bin and its zero padding) in full 32-byte sectors: a lone 2- or
           // 4-byte store per frame and step is a read-modify-write in the memory system (measured: 5 % of the launch)
@@ -1403,7 +1409,7 @@ int vn_launch_tchain(vaenmf_plan* p, const VnChainCall& cc, hipStream_t st) {
   ChainArgs a = {};
   a.dw = make_decw(p);
   a.X2 = cc.X2; a.W = cc.W; a.Ht = cc.Ht; a.g = cc.g; a.B1 = cc.B1; a.Z = cc.Z; a.Zs = cc.Zs; a.acc_out = cc.acc_out; a.Vb = p->Vb_ext;
-  a.VsS = cc.VsS; a.src = cc.src; a.Rs = cc.Rs;
+  a.VsS = cc.VsS; a.src = cc.src; a.Rs = cc.Rs; a.lay = cc.lay;
   a.tile_utt = p->d_tile_utt; a.tile_n0 = p->d_tile_n0; a.tile_cnt = p->d_tile_cnt; a.frame_off = p->d_frame_off;
   a.utt_seed = p->d_utt_seed; a.eps = cc.eps; a.u = cc.u;
   a.Fs = p->Fs; a.Kp = p->Kp; a.NT = p->NT; a.Rcap = cc.Rcap; a.nsamples = cc.nsamples; a.burnin = cc.burnin;

@@ -36,6 +36,7 @@ VnSwitches vn_switches() {
   s.wfused_grid = atoi(env("VAENMF_WFUSED_GRID"));
   s.grid_cap = atoi(env("VAENMF_GRID_CAP"));
   s.keep_zs = env("VAENMF_KEEP_ZS")[0] == '1';
+  s.store_aligned = env("VAENMF_STORE_ALIGNED")[0] != '0';
   return s;
 }
 
@@ -144,7 +145,7 @@ extern "C" int vaenmf_plan_create(const vaenmf_config* cfg, vaenmf_plan** out) {
   const size_t nk1 = p->Lp / 32, nt3 = p->wide ? p->Fs / 16 : p->NT3;
   p->have_weights = false;
   p->Vb_ext = nullptr;
-  p->store_on = false; p->VsS = nullptr; p->src = nullptr; p->VsS_cap = p->src_cap = 0; p->store_R = p->store_Rs = 0;
+  p->store_on = false; p->VsS = nullptr; p->src = nullptr; p->VsS_cap = p->src_cap = 0; p->store_R = p->store_Rs = 0; p->store_lay = {};
   p->n_utt = p->NT = p->n_tiles = 0;
   p->prof_on = false;
   p->prof_used = 0;
@@ -226,6 +227,7 @@ extern "C" int vaenmf_plan_query(const vaenmf_plan* p, int32_t what) {
     case VAENMF_Q_W_FUSED: return p->last_w_fused;
     case VAENMF_Q_CHAIN_KERNEL: return p->last_chain_kernel;
     case VAENMF_Q_LP: return p->Lp;
+    case VAENMF_Q_STORE_ALIGNED: return p->store_lay.aligned;
     default: return -1;
   }
 }

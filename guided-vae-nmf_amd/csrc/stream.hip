@@ -43,7 +43,9 @@ constexpr int ST_WAVES = 4;      // minimum waves per SIMD asked of the compiler
 constexpr int ROW_AUX = 2;       // (buffer loads: 2 = nt)
 
 struct StreamArgs {
-  const void* VsS;             // [NT][Rs][Fs], float or bf16 (template ST)
+  const void* VsS;             // the rows of (frame, slot) and their odd bins F-1, float or bf16 (template ST), laid out as `lay`
+  VnStoreLayout lay;           // (common.h) every address into VsS comes from here
+  unsigned store_bytes;        // bytes of VsS the NT frames take, both regions (buffer resources)
   const int32_t* src;          // [Rs][NT] (sample-major)
   const float *X2, *W, *normW, *Vb, *X;
   float *Ht, *g, *A1, *P, *S_hat, *N_hat, *WFs, *WFn;
@@ -106,6 +108,20 @@ struct FrameCtx {
     wx = 0.f;
     nw = 1.f;
     in_lds = false;
+  }
+  // The store's layout, read from the kernel's argument block where it is used -- the kernel takes its StreamArgs as the one
+  // by-value argument, so `lay` lies at the same offset there -- through a pointer the compiler cannot see through.  Taken
+  // from `a`, the fields are scalars kept across the frame loop, and hg_stream_kernel at four wavefronts per SIMD has none
+  // to spare (all 102 in use: three more spilled to vector registers, and two vector registers to scratch with them).
+  __device__ __forceinline__ VnStoreLayout lay_here() const {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef const __attribute__((address_space(4))) char* kptr;
+    kptr kp = (kptr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kp));
+    return *(const __attribute__((address_space(4))) VnStoreLayout*)(kp + offsetof(StreamArgs, lay));
+#else
+    return a.lay;
+#endif
   }
   // bin t of chunk c is a real bin (without TAIL: Fm is a multiple of 4 and the chunk is valid as a whole)
   __device__ __forceinline__ bool ok(int c, int t) const { return TAIL ? t < nb[c] : cv[c]; }
@@ -315,8 +331,6 @@ struct RowBatch {
   unsigned xbits;              // lane j: extra bin (F-1) of row j of the batch, as loaded (bf16 bits in the low half / float bits);
                                // x() converts at the use, so no load site waits for it before issuing the row loads
   int nr;
-  // rows r0 .. r0+nr-1 of the frame whose store block starts at `base`; scol = the frame's column of the
-  // sample-major slot map (stride NT)
   // lane j: slot of row r0 + j of the frame (the frame's column of the sample-major slot map, stride NT)
   template <typename FC>
   static __device__ __forceinline__ int load_slots(const FC& fc, const int32_t* scol, int r0, int R) {
@@ -324,9 +338,11 @@ struct RowBatch {
     // (a 32-bit BYTE offset from a uniform base: SGPR pair + one VGPR, no 64-bit address pair kept -- and spilled -- per lane)
     return *reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(scol) + (unsigned)(r0 + (fc.lane < nr_ ? fc.lane : 0)) * (unsigned)fc.a.NT * 4u);
   }
-  // rows r0 .. r0+nr-1 of the frame whose store block starts at `base`, slots from load_slots
+  // rows r0 .. r0+nr-1 of frame n, slots from load_slots
   template <typename FC>
-  __device__ __forceinline__ void load_rows(const FC& fc, const ST* base, int sl, int r0, int R) {
+  __device__ __forceinline__ void load_rows(const FC& fc, int n, int sl, int r0, int R) {
+    const VnStoreLayout lay = fc.lay_here();
+    const ST* base = reinterpret_cast<const ST*>(fc.a.VsS) + (size_t)n * lay.frame;
     nr = RT > 0 ? RT : (R - r0 < RB ? R - r0 : RB);
     // (row 0 exists in every batch and is loaded without a check: its readlane of `sl` puts the wait for the slot
     // load on the straight path -- behind a branch, the compiler waits with vmcnt(0) in EVERY row's block, i.e. for
@@ -334,31 +350,35 @@ struct RowBatch {
 #pragma unroll
     for (int r = 0; r < RB; ++r)
       if (r == 0 || on(r)) {
-        const ST* row = base + (size_t)__builtin_amdgcn_readlane(sl, r) * fc.a.Fs;
+        const ST* row = base + (size_t)__builtin_amdgcn_readlane(sl, r) * lay.row;
 #pragma unroll
         for (int c = 0; c < NCH; ++c) raw[r][c] = __builtin_nontemporal_load(reinterpret_cast<const raw_t*>(row + fc.fo[c]));
       }
     // extra bin, raw bits (x() converts at the use: a conversion here would wait for every load above)
     if (fc.has_x) {
-      if constexpr (sizeof(ST) == 2) xbits = reinterpret_cast<const unsigned short*>(base)[(size_t)sl * fc.a.Fs + fc.a.F - 1];
-      else xbits = reinterpret_cast<const unsigned*>(base)[(size_t)sl * fc.a.Fs + fc.a.F - 1];
+      // (uniform base + a 32-bit byte offset per lane: one VGPR of address, not a 64-bit pair)
+      const char* xrow = reinterpret_cast<const char*>(reinterpret_cast<const ST*>(fc.a.VsS) + lay.xbase + (size_t)n * lay.xframe);
+      const unsigned xo = (unsigned)sl * (lay.xslot * (unsigned)sizeof(ST));
+      if constexpr (sizeof(ST) == 2) xbits = *reinterpret_cast<const unsigned short*>(xrow + xo);
+      else xbits = *reinterpret_cast<const unsigned*>(xrow + xo);
     } else xbits = 0u;
   }
   template <typename FC>
-  __device__ __forceinline__ void load(const FC& fc, const ST* base, const int32_t* scol, int r0, int R) {
-    load_rows(fc, base, load_slots(fc, scol, r0, R), r0, R);
+  __device__ __forceinline__ void load(const FC& fc, int n, const int32_t* scol, int r0, int R) {
+    load_rows(fc, n, load_slots(fc, scol, r0, R), r0, R);
   }
   // The same through a buffer resource over the whole store (below 4 GB): a row's address is the resource (SGPRs) +
   // this lane's constant byte offset (one VGPR) + a scalar offset built from the row's slot -- no 64-bit address
   // pair per row in vector registers (thirty of them per frame spilled in the pipelined kernels).
   template <typename FC>
-  __device__ __forceinline__ void load_rows_buf(const FC& fc, __amdgpu_buffer_rsrc_t rs, unsigned frame_off, int sl, int R, int r0 = 0) {
+  __device__ __forceinline__ void load_rows_buf(const FC& fc, __amdgpu_buffer_rsrc_t rs, int n, int sl, int R, int r0 = 0) {
     nr = RT > 0 ? RT : (R - r0 < RB ? R - r0 : RB);
-    const unsigned rowb = (unsigned)fc.a.Fs * (unsigned)sizeof(ST);
+    const unsigned frame_off = (unsigned)n * fc.a.lay.frame * (unsigned)sizeof(ST);
+    const unsigned rowb = fc.a.lay.row * (unsigned)sizeof(ST);
     // (raw bits: the conversion would wait for this load before the row loads below are even issued; x()
     // converts at the first use, a frame later)
     if (fc.has_x) {
-      const unsigned o = frame_off + (unsigned)sl * rowb + (unsigned)(fc.a.F - 1) * (unsigned)sizeof(ST);
+      const unsigned o = ((unsigned)fc.a.lay.xbase + (unsigned)n * fc.a.lay.xframe + (unsigned)sl * fc.a.lay.xslot) * (unsigned)sizeof(ST);
       if constexpr (sizeof(ST) == 2) xbits = (unsigned)__builtin_amdgcn_raw_buffer_load_b16(rs, o, 0, 0);
       else xbits = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rs, o, 0, 0);
     } else xbits = 0u;
@@ -440,11 +460,10 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1) ? ST_WAVES : 2) void wst
     // The frame fits two half batches, each refilled with the NEXT frame's rows as soon as it has been
     // consumed, so that half a frame of loads is in flight while the other half is computed.
     Half h0, h1;
-    auto base_of = [&](int n) { return reinterpret_cast<const ST*>(a.VsS) + (size_t)n * a.Rs * a.Fs; };
     const int R0 = a.R < HB ? a.R : HB;              // rows of the first half
     if (n_beg < n_end) {
-      h0.load(fc, base_of(n_beg), a.src + n_beg, 0, R0);
-      if (a.R > HB) h1.load(fc, base_of(n_beg), a.src + n_beg, HB, a.R); else h1.nr = 0, h1.xbits = 0u;
+      h0.load(fc, n_beg, a.src + n_beg, 0, R0);
+      if (a.R > HB) h1.load(fc, n_beg, a.src + n_beg, HB, a.R); else h1.nr = 0, h1.xbits = 0u;
     }
     for (int n = n_beg; n < n_end; ++n) {
       const int utt = a.frame_utt[n];
@@ -482,10 +501,10 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1) ? ST_WAVES : 2) void wst
         a2x += wave_sum(q * q);
       };
       consume(h0);
-      if (n + 1 < n_end) h0.load(fc, base_of(n + 1), a.src + n + 1, 0, R0);
+      if (n + 1 < n_end) h0.load(fc, n + 1, a.src + n + 1, 0, R0);
       if (a.R > HB) {
         consume(h1);
-        if (n + 1 < n_end) h1.load(fc, base_of(n + 1), a.src + n + 1, HB, a.R);
+        if (n + 1 < n_end) h1.load(fc, n + 1, a.src + n + 1, HB, a.R);
       }
 #pragma unroll
       for (int c = 0; c < NCH; ++c)
@@ -497,10 +516,9 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1) ? ST_WAVES : 2) void wst
     return;
   }
   for (int n = n_beg; n < n_end; ++n) {
-    const ST* base = reinterpret_cast<const ST*>(a.VsS) + (size_t)n * a.Rs * a.Fs;
     const int32_t* srow = a.src + n;
     RBt rb;
-    rb.load(fc, base, srow, 0, a.R);                 // (issued first: the longest latency of the frame)
+    rb.load(fc, n, srow, 0, a.R);                 // (issued first: the longest latency of the frame)
     const int utt = a.frame_utt[n];
     fc.set_utt(utt);
     const float gn = a.g[n];
@@ -518,7 +536,7 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1) ? ST_WAVES : 2) void wst
 #pragma unroll
     for (int c = 0; c < NCH; ++c) a1[c] = a2[c] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int r0 = 0; r0 < a.R; r0 += RBt::RB) {
-      if (r0 > 0) rb.load(fc, base, srow, r0, a.R);
+      if (r0 > 0) rb.load(fc, n, srow, r0, a.R);
 #pragma unroll
       for (int r = 0; r < RBt::RB; ++r)
         if (r < rb.nr) {
@@ -560,7 +578,6 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1 && sizeof(ST) == 2) ? ST_
   wave_frames(a.NT, n_beg, n_end);
   const bool one = a.R <= RBt::RB;                    // the frame fits one batch: its rows are read once
   for (int n = n_beg; n < n_end; ++n) {
-    const ST* base = reinterpret_cast<const ST*>(a.VsS) + (size_t)n * a.Rs * a.Fs;
     const int32_t* srow = a.src + n;
     RBt rb;
     // Order of the frame's requests (vmcnt counts in order, and behind the per-row branches the compiler can only wait
@@ -585,7 +602,7 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1 && sizeof(ST) == 2) ? ST_
       }
     }
     fc.set_utt(utt, a.gains_only ? nullptr : a.normW);
-    rb.load_rows(fc, base, sl, 0, a.R);
+    rb.load_rows(fc, n, sl, 0, a.R);
     const f32x2 gn2 = {gn, gn};
     if (!a.gains_only) {
       // ---- H update (mcem.py:118-121): W already updated and normalised; H carries the pending column norms
@@ -599,7 +616,7 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1 && sizeof(ST) == 2) ? ST_
 #pragma unroll
       for (int c = 0; c < NCH; ++c) a1[c] = a2[c] = f32x4{0.f, 0.f, 0.f, 0.f};
       for (int r0 = 0; r0 < a.R; r0 += RBt::RB) {
-        if (r0 > 0) rb.load(fc, base, srow, r0, a.R);
+        if (r0 > 0) rb.load(fc, n, srow, r0, a.R);
         auto row1 = [&](int r) {
           f32x4 v[NCH];
           rb.get(r, v);
@@ -646,7 +663,7 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1 && sizeof(ST) == 2) ? ST_
 #pragma unroll
       for (int c = 0; c < NCH; ++c) ng[c] = dg[c] = f32x4{0.f, 0.f, 0.f, 0.f};
       for (int r0 = 0; r0 < a.R; r0 += RBt::RB) {
-        if (!one) rb.load(fc, base, srow, r0, a.R);
+        if (!one) rb.load(fc, n, srow, r0, a.R);
         auto row2 = [&](int r) {
           f32x4 v[NCH];
           rb.get(r, v);
@@ -685,7 +702,7 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1 && sizeof(ST) == 2) ? ST_
 #pragma unroll
     for (int c = 0; c < NCH; ++c) cl[c] = cx[c] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int r0 = 0; r0 < a.R; r0 += RBt::RB) {
-      if (!one) rb.load(fc, base, srow, r0, a.R);
+      if (!one) rb.load(fc, n, srow, r0, a.R);
 #pragma unroll
       for (int r = 0; r < RBt::RB; r += 2) {
         if (rb.on(r + 1)) {
@@ -739,10 +756,9 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1) ? ST_WAVES : 2) void wf_
   wave_frames(a.NT, n_beg, n_end);
   const float invR = 1.0f / (float)a.R;
   for (int n = n_beg; n < n_end; ++n) {
-    const ST* base = reinterpret_cast<const ST*>(a.VsS) + (size_t)n * a.Rs * a.Fs;
     const int32_t* srow = a.src + n;
     RBt rb;
-    rb.load(fc, base, srow, 0, a.R);
+    rb.load(fc, n, srow, 0, a.R);
     const int utt = a.frame_utt[n];
     fc.set_utt(utt);
     const float gn = a.g[n];
@@ -765,7 +781,7 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1) ? ST_WAVES : 2) void wf_
 #pragma unroll
     for (int c = 0; c < NCH; ++c) ws[c] = wn[c] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int r0 = 0; r0 < a.R; r0 += RBt::RB) {
-      if (r0 > 0) rb.load(fc, base, srow, r0, a.R);
+      if (r0 > 0) rb.load(fc, n, srow, r0, a.R);
 #pragma unroll
       for (int r = 0; r < RBt::RB; ++r)
         if (r < rb.nr) {
@@ -843,7 +859,7 @@ __global__ __launch_bounds__(256, 2) void wstats_stream2_kernel(const StreamArgs
   int n_beg, n_end;
   wave_frames(a.NT, n_beg, n_end);
   if (n_beg >= n_end) return;
-  __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.VsS), 0, (int)((unsigned)a.NT * (unsigned)(a.Rs * a.Fs) * (unsigned)sizeof(ST)), 0x00020000);
+  __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.VsS), 0, (int)a.store_bytes, 0x00020000);
   // slots are requested TWO frames ahead, rows and operands one frame ahead: the row addresses depend on the slots,
   // and a wait for the slots placed between two frames' row loads would expose a full memory round trip per frame
   auto request = [&](int n, RBt& rb, FS& s, int sl) {
@@ -851,7 +867,7 @@ __global__ __launch_bounds__(256, 2) void wstats_stream2_kernel(const StreamArgs
     s.g = a.g[n];
     s.hl = a.Ht[(size_t)n * KP + (fc.lane < KP ? fc.lane : 0)];
     fc.load_x2(n, s.x2, s.x2x);
-    rb.load_rows_buf(fc, vrs, (unsigned)n * (unsigned)(a.Rs * a.Fs) * (unsigned)sizeof(ST), sl, a.R);
+    rb.load_rows_buf(fc, vrs, n, sl, a.R);
   };
   auto compute = [&](int n, RBt& rb, const FS& s) {
     fc.set_utt(s.utt);
@@ -929,7 +945,8 @@ struct RotCtx {
   const StreamArgs& a;
   const FC& fc;
   __amdgpu_buffer_rsrc_t vrs;
-  unsigned rowb, frameb, voff, xvoff;
+  unsigned rowb, frameb, voff;
+  unsigned xslotb, xframeb, xvoff;   // the odd bin F-1 of (frame n, slot s): byte xvoff + n xframeb + s xslotb
   const char* pk_base;         // per-lane base and stride (bytes per frame) of the packed small-operand load
   unsigned pk_stride;
   // two register sets: the frame in set S is consumed while set 1-S is refilled with the next frame's rows, row by
@@ -939,11 +956,11 @@ struct RotCtx {
   bf16x4 raw[2][RT];
   unsigned xb[2];              // lane j < RT: bf16 bits of the extra bin of row j
   __device__ RotCtx(const StreamArgs& a_, const FC& fc_) : a(a_), fc(fc_) {
-    vrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.VsS), 0, (int)((unsigned)a.NT * (unsigned)(a.Rs * a.Fs) * 2u), 0x00020000);
-    rowb = (unsigned)a.Fs * 2u;
-    frameb = (unsigned)a.Rs * rowb;
+    vrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.VsS), 0, (int)a.store_bytes, 0x00020000);
+    rowb = a.lay.row * 2u;
+    frameb = a.lay.frame * 2u;
     voff = (unsigned)(fc.cv[0] ? fc.f0[0] : 0) * 2u;
-    xvoff = (unsigned)(a.F - 1) * 2u;
+    xslotb = a.lay.xslot * 2u; xframeb = a.lay.xframe * 2u; xvoff = (unsigned)a.lay.xbase * 2u;
     xb[0] = xb[1] = 0u;
     const int l = fc.lane;
     if (l == KP) { pk_base = reinterpret_cast<const char*>(a.frame_utt); pk_stride = 4u; }
@@ -974,7 +991,7 @@ struct RotCtx {
   }
   template <int S>
   __device__ __forceinline__ void req_x(int n, int sl, bool on) {
-    if (fc.has_x) xb[S] = (unsigned)__builtin_amdgcn_raw_buffer_load_b16(vrs, on ? (unsigned)sl * rowb + xvoff : 0xF0000000u, (unsigned)n * frameb, 0);
+    if (fc.has_x) xb[S] = (unsigned)__builtin_amdgcn_raw_buffer_load_b16(vrs, on ? (unsigned)sl * xslotb + xvoff : 0xF0000000u, (unsigned)n * xframeb, 0);
   }
   template <int S>
   __device__ __forceinline__ f32x4 row(int r) const {
@@ -1173,7 +1190,6 @@ __global__ __launch_bounds__(256, 2) void wstats_group_kernel(const StreamArgs a
       a1xs[i] = pxs[i] = hls[i] = 0.f;
       const int n = n_beg + i;
       if (n < n_end) {
-        const ST* base = reinterpret_cast<const ST*>(a.VsS) + (size_t)n * a.Rs * a.Fs;
         const int sl = RBt::load_slots(fc, a.src + n, 0, RT);
         const float gn = a.g[n];
         f32x4 x2[1];
@@ -1189,7 +1205,7 @@ __global__ __launch_bounds__(256, 2) void wstats_group_kernel(const StreamArgs a
         hls[i] = fc.lane < KP ? a.Ht[(size_t)n * KP + (fc.lane < KP ? fc.lane : 0)] : 0.f;      // lane k: H[k, n]
         fc.set_utt(utt);
         RBt rb;
-        rb.load_rows(fc, base, sl, 0, RT);
+        rb.load_rows(fc, n, sl, 0, RT);
         f32x4 vb[1], a1, a2;
         float vbx;
         fc.noise_var(utt, h, vb, vbx);
@@ -1263,6 +1279,8 @@ StreamArgs base_args(const vaenmf_plan* p) {
   a.VsS = p->VsS; a.src = p->src; a.frame_utt = p->d_frame_utt; a.Vb = p->Vb_ext;
   a.store_f32 = p->cfg.precision == VAENMF_PREC_BF16X3;
   a.n_sms = p->n_sms;
+  a.lay = p->store_lay;
+  a.store_bytes = (unsigned)((a.lay.aligned ? a.lay.xbase + (uint64_t)p->NT * a.lay.xframe : (uint64_t)p->NT * a.lay.frame) * (a.store_f32 ? 4 : 2));
   a.NT = p->NT; a.R = p->store_R; a.Rs = p->store_Rs; a.F = p->cfg.F; a.Fm = p->Fm; a.Fs = p->Fs; a.K = p->cfg.K;
   return a;
 }

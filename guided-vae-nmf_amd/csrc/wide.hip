@@ -36,6 +36,7 @@ struct WideArgs {
   const float *X2, *W, *Ht, *g, *B1, *Vb;
   float *Z, *Zs, *acc_out;
   void* VsS; int32_t* src; int Rs;
+  VnStoreLayout lay;               // of VsS (common.h)
   const int32_t *wt_utt, *wt_n0, *wt_cnt, *frame_off;
   const uint64_t* utt_seed;
   const float *eps, *u;
@@ -208,7 +209,7 @@ __global__ __launch_bounds__(256) void widechain_kernel(const WideArgs a) {
     }
     // ---- output layer and the frame's energy
     const char* last = a.NT2 > 0 ? act2 : act1;
-    char* const vrow = DOST ? reinterpret_cast<char*>(a.VsS) + ((size_t)nrow * a.Rs + slot) * a.Fs * sizeof(store_t) : nullptr;
+    char* const vrow = DOST ? reinterpret_cast<char*>(a.VsS) + ((size_t)nrow * a.lay.frame + (size_t)slot * a.lay.row) * sizeof(store_t) : nullptr;
     double e = 0.0;
 #pragma unroll
     for (int i = 0; i < WD_MAXT; ++i) {
@@ -230,7 +231,10 @@ __global__ __launch_bounds__(256) void widechain_kernel(const WideArgs a) {
           pl += fast_log2(vx);
           px += x2[i][k] * fast_rcp(vx);
         }
-        if (DOST && fvalid) {
+        if (DOST && fvalid && 16 * t + 4 * q >= (int)a.lay.row) {      // line-aligned layout: a row ends at bin F-2, bin F-1 has its own block
+          if (16 * t + 4 * q == a.F - 1)
+            reinterpret_cast<store_t*>(a.VsS)[a.lay.xbase + (size_t)nrow * a.lay.xframe + (size_t)slot * a.lay.xslot] = (store_t)ev[0];
+        } else if (DOST && fvalid) {
           store_t* dst = reinterpret_cast<store_t*>(vrow) + 16 * t + 4 * q;
           if (SPLIT) *reinterpret_cast<f32x4*>(dst) = ev;
           else *reinterpret_cast<bf16x4*>(dst) = bf16x4{(__bf16)ev[0], (__bf16)ev[1], (__bf16)ev[2], (__bf16)ev[3]};
@@ -339,7 +343,7 @@ int vn_launch_widechain(vaenmf_plan* p, const VnChainCall& cc, hipStream_t st) {
   a.F = p->cfg.F; a.Fs = p->Fs; a.Kp = p->Kp; a.NT = p->NT;
   a.X2 = cc.X2; a.W = cc.W; a.Ht = cc.Ht; a.g = cc.g; a.B1 = cc.B1; a.Vb = p->Vb_ext;
   a.Z = cc.Z; a.Zs = cc.Zs; a.acc_out = cc.acc_out;
-  a.VsS = cc.VsS; a.src = cc.src; a.Rs = cc.Rs;
+  a.VsS = cc.VsS; a.src = cc.src; a.Rs = cc.Rs; a.lay = cc.lay;
   a.wt_utt = p->d_wt_utt; a.wt_n0 = p->d_wt_n0; a.wt_cnt = p->d_wt_cnt; a.frame_off = p->d_frame_off;
   a.utt_seed = p->d_utt_seed; a.eps = cc.eps; a.u = cc.u;
   a.Rcap = cc.Rcap; a.nsamples = cc.nsamples; a.burnin = cc.burnin; a.rng_mode = cc.rng_mode; a.update_Z = cc.update_Z;

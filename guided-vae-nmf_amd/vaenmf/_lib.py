@@ -8,7 +8,7 @@ LIB_PATH = os.environ.get("VAENMF_LIB") or os.path.join(_HERE, "libvaenmf.so")  
 
 PREC_BF16X3, PREC_BF16 = 0, 1
 RNG_REPLAY, RNG_DEVICE = 0, 1
-Q_FS, Q_KP, Q_TILES, Q_NT, Q_NUTT, Q_MSTEP_PATH, Q_WTILES, Q_EM_GRAPH, Q_DEV_ALLOCS, Q_W_FUSED, Q_CHAIN_KERNEL, Q_LP = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
+Q_FS, Q_KP, Q_TILES, Q_NT, Q_NUTT, Q_MSTEP_PATH, Q_WTILES, Q_EM_GRAPH, Q_DEV_ALLOCS, Q_W_FUSED, Q_CHAIN_KERNEL, Q_LP, Q_STORE_ALIGNED = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12
 ACT_NONE, ACT_TANH, ACT_RELU, ACT_SIGMOID, ACT_STEP = 0, 1, 2, 3, 4
 LABEL_IBM, LABEL_VAD = 0, 1
 
@@ -76,6 +76,7 @@ SIGNATURES = {
     "vaenmf_profile_enable": (_I, [_P, _I]),
     "vaenmf_profile_read": (_I, [_P, _P, _P]),
     "vaenmf_wchain_addressable": (_I, [_I64, _I, _I, _I, _I, _I, _I]),
+    "vaenmf_store_layout": (_I, [_I, _I, _I, _I, _I64, _I, _P]),
     "vaenmf_hbm_read_probe": (_I, [_P, _I64, _I, _P, C.POINTER(_D), _P]),
 }
 

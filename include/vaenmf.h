@@ -112,6 +112,7 @@ enum { VAENMF_Q_FS = 0, VAENMF_Q_KP = 1, VAENMF_Q_TILES = 2, VAENMF_Q_NT = 3, VA
                                       2 = four wavefronts per 16 frames (bench shape, batches of at most one wave tile per CU),
                                       3 = the wide-decoder kernel (a workgroup of four wavefronts per 16 frames; wide plans only) */
        VAENMF_Q_LP = 11,         /* latent columns Lp of Z, Zs and the replay draws: 32, or 128 on a wide plan (L > 32 or a hidden layer of 256) */
+       VAENMF_Q_STORE_ALIGNED = 12, /* 1 when the last MH chain that filled the sample store wrote the line-aligned layout (vaenmf_store_layout) */
        VAENMF_Q_DEV_ALLOCS = 8 };/* device allocations the library has made in this process so far (any plan): a caller that
                                     reuses a plan can check that a call allocated nothing */
 
@@ -266,7 +267,8 @@ int vaenmf_dense(const float* X, int32_t M, int32_t in, int32_t ldx, const float
  * bf16x3 mode, bf16 rows in bf16 mode (half the traffic; rounding of the size the bf16
  * decoder products carry anyway) -- and a map
  * src DEV int32 [Rs][NT]: the variances of sample r of frame n (the state after post-burn-in
- * step r, mcem.py:429-437) are the row VsS[n][src[r][n]].  The M-step and the Wiener
+ * step r, mcem.py:429-437) are the row VsS[n][src[r][n]] (at F = 257 and 513 the rows are kept on whole 128-byte lines,
+ * without their odd last bin: vaenmf_store_layout below).  The M-step and the Wiener
  * filter can then stream the samples' variances from HBM instead of decoding Zs again
  * (vaenmf_m_step_stored, vaenmf_wiener_stored; vaenmf_em_run does so by itself).  The store
  * describes the most recent vaenmf_mh_chain call only.  vaenmf_sample_store_gather copies
@@ -278,6 +280,13 @@ int vaenmf_dense(const float* X, int32_t M, int32_t in, int32_t ldx, const float
  * vaenmf_mh_chain never allocates: it fails with a message if the store is too small for its batch. */
 int vaenmf_sample_store(vaenmf_plan* plan, int32_t max_samples);
 int vaenmf_sample_store_gather(vaenmf_plan* plan, float* Vs_out, void* stream);
+/* Where the store keeps its rows, in elements of elt_bytes (2: bf16 rows, 4: float rows).  Bin f < row of (frame n, slot s)
+ * is element n * frame + s * row + f; bin F-1 is element xbase + n * xframe + s * xslot.  With aligned != 0 and F = 257 or
+ * 513 a row holds bins 0..F-2 alone (whole 128-byte lines) and the odd bins F-1 of a frame's Rs slots form one block padded
+ * to 64 bytes, the blocks behind the rows of all `frames` frame blocks; otherwise a row is Fs elements with bin F-1 inside it.
+ * HOST out7: row, frame, xslot, xframe, xbase, aligned (the layout in effect), bytes of the whole store.  Pure host
+ * arithmetic (no GPU needed).  The library picks the aligned layout by itself; VAENMF_STORE_ALIGNED=0 keeps the padded one. */
+int vaenmf_store_layout(int32_t F, int32_t Fs, int32_t elt_bytes, int32_t Rs, int64_t frames, int32_t aligned, int64_t* out7);
 /* vaenmf_m_step / vaenmf_wiener over the store of the most recent chain (same updates, same
  * outputs; the samples are the store's, so no Zs / B1 arguments). */
 int vaenmf_m_step_stored(vaenmf_plan* plan, const float* X2, float* W, float* Ht, float* g,
