@@ -73,6 +73,12 @@ SIGNATURES = {
     "vaenmf_spp_estimate": (_I, [_P, _I, _I, _P, _I, _D, _D, _D, _D, _I, _P, _P, _I, _P]),
     "vaenmf_spp_noise_given": (_I, [_P, _P, _I64, _D, _P, _P]),
     "vaenmf_gram3_batch": (_I, [_P, _P, _P, _I, _P, _P, _P]),
+    "vaenmf_stoi_geometry": (_I, [_I64, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+    "vaenmf_stoi_bands": (_I, [_P, _P]),
+    "vaenmf_stoi_work_bytes": (_I64, [_I, _P]),
+    "vaenmf_stoi_tob": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "vaenmf_stoi_segments": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _I64, _P]),
+    "vaenmf_stoi_batch": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _I64, _P]),
     "vaenmf_profile_enable": (_I, [_P, _I]),
     "vaenmf_profile_read": (_I, [_P, _P, _P]),
     "vaenmf_wchain_addressable": (_I, [_I64, _I, _I, _I, _I, _I, _I]),

@@ -1,6 +1,9 @@
 """SI-SDR / SI-SIR / SI-SAR (python/metrics.py:12-60) from float64 Gram sums computed
-on the GPU (vaenmf_gram3_batch), the statistics table (metrics.py:5-10, 70-108) and
+on the GPU (vaenmf_gram3_batch), STOI / ESTOI (pystoi's stoi as scripts/run_metrics_M2.py:117 calls it) in one batched
+device pass (vaenmf_stoi_batch), the statistics table (metrics.py:5-10, 70-108) and
 the sufficient statistics that are all-reduced over ranks."""
+import ctypes as C
+
 import numpy as np
 import torch
 
@@ -8,6 +11,8 @@ from ._lib import check, lib
 from .engine import _ptr, _stream
 
 METRIC_KEYS = ("SI-SDR", "SI-SIR", "SI-SAR")
+METRIC_KEYS_ESTOI = METRIC_KEYS + ("ESTOI",)
+STOI_FS = 10000
 
 
 def ratios_from_gram(G):
@@ -55,6 +60,71 @@ def energy_ratios(s_hat, s, n):
     return float(r[0]), float(r[1]), float(r[2])
 
 
+def stoi_geometry(n_samples):
+    """(n_frames, max_spec_frames, max_segments) of n_samples samples at 10 kHz (vaenmf_stoi_geometry)."""
+    v = [C.c_int32() for _ in range(3)]
+    check(lib().vaenmf_stoi_geometry(int(n_samples), *[C.byref(c) for c in v]))
+    return tuple(c.value for c in v)
+
+
+def stoi_bands():
+    """(lo, hi): numpy int32 [15], the FFT bins lo <= bin < hi of the 15 third-octave bands (vaenmf_stoi_bands)."""
+    lo, hi = np.empty(15, np.int32), np.empty(15, np.int32)
+    check(lib().vaenmf_stoi_bands(lo.ctypes.data, hi.ctypes.data))
+    return lo, hi
+
+
+def stoi_offsets(sample_counts):
+    """Host int64 [U+1] sample offsets of a concatenated batch, as the vaenmf_stoi_* calls take them."""
+    return np.concatenate([[0], np.cumsum([int(t) for t in sample_counts], dtype=np.int64)]).astype(np.int64)
+
+
+def stoi_work(offsets, device):
+    """The scratch buffer of the vaenmf_stoi_* calls for a batch with these offsets."""
+    n = lib().vaenmf_stoi_work_bytes(len(offsets) - 1, offsets.ctypes.data)
+    if n < 0:
+        raise ValueError(lib().vaenmf_last_error().decode())
+    return torch.empty(max(int(n), 8), dtype=torch.uint8, device=device)
+
+
+def stoi_batch_device(clean, proc, sample_counts, fs, extended=True):
+    """clean, proc: device float32 [sum T] (utterances concatenated, equal lengths per utterance) at fs Hz -> DEVICE
+    float64 [U]: ESTOI (extended) or classic STOI per utterance, no synchronisation.  Signals at another rate than 10 kHz
+    go through resample_batch (its default taps) first.  An utterance's score does not depend on its batch; one with fewer
+    than 30 frames after silence removal scores 1e-5."""
+    from .resample import _rate, resample_batch
+    dev = clean.device
+    for name, t in (("clean", clean), ("proc", proc)):
+        if t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != sum(int(c) for c in sample_counts) or t.device != dev:
+            raise ValueError("%s must be float32 [sum of sample_counts = %d] on %s, got %s %s on %s"
+                             % (name, sum(int(c) for c in sample_counts), dev, t.dtype, tuple(t.shape), t.device))
+    if _rate(fs, "fs") != STOI_FS:
+        clean, counts = resample_batch(clean.contiguous(), sample_counts, fs, STOI_FS, device=dev)
+        proc, _ = resample_batch(proc.contiguous(), sample_counts, fs, STOI_FS, device=dev)
+        sample_counts = counts
+    off = stoi_offsets(sample_counts)
+    d = torch.empty(len(sample_counts), device=dev, dtype=torch.float64)
+    work = stoi_work(off, dev)
+    check(lib().vaenmf_stoi_batch(_ptr(clean.contiguous()), _ptr(proc.contiguous()), len(sample_counts), off.ctypes.data,
+                                  1 if extended else 0, _ptr(d), None, _ptr(work), work.numel(), _stream()))
+    return d
+
+
+def stoi_batch(clean, proc, sample_counts, fs, extended=True):
+    """stoi_batch_device -> numpy float64 [U]."""
+    return stoi_batch_device(clean, proc, sample_counts, fs, extended).cpu().numpy()
+
+
+def stoi(x, y, fs_sig, extended=False):
+    """pystoi's signature (scripts/run_metrics_M2.py:117 calls it with extended=True): numpy time signals of equal length
+    -> float.  Two deviations from pystoi (include/vaenmf.h): no dither, and the project's resampling filter."""
+    x, y = np.asarray(x), np.asarray(y)
+    if x.shape != y.shape or x.ndim != 1:
+        raise ValueError("x and y should have the same length, found %s and %s" % (x.shape, y.shape))
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
+    return float(stoi_batch(t(x), t(y), [len(x)], fs_sig, extended)[0])
+
+
 def mean_confidence_interval(data, confidence=0.95, round=3):
     """metrics.py:5-10."""
     import scipy.stats
@@ -68,10 +138,13 @@ def mean_confidence_interval(data, confidence=0.95, round=3):
 def sufficient_stats(values, snr_db, snr_bins=(-5.0, 0.0, 5.0)):
     """values [U,3] (SI-SDR,SI-SIR,SI-SAR), snr_db [U] -> float64 [(1+len(bins)),3,3] of
     (count, sum, sum of squares): what the ranks all-reduce (sum) so that rank 0 can print
-    mean +- t-CI overall and per input SNR (metrics.py:70-108)."""
-    values = np.asarray(values, dtype=np.float64).reshape(-1, 3)
+    mean +- t-CI overall and per input SNR (metrics.py:70-108).  values [U,4] (with ESTOI, METRIC_KEYS_ESTOI) gives
+    [(1+len(bins)),4,3] in the same form."""
+    values = np.asarray(values, dtype=np.float64)
+    nm = values.shape[1] if values.ndim == 2 and values.shape[1] == len(METRIC_KEYS_ESTOI) else len(METRIC_KEYS)
+    values = values.reshape(-1, nm)
     snr_db = np.asarray(snr_db, dtype=np.float64)
-    out = np.zeros((1 + len(snr_bins), 3, 3))
+    out = np.zeros((1 + len(snr_bins), nm, 3))
     groups = [np.ones(len(values), bool)] + [snr_db == b for b in snr_bins]
     for gi, m in enumerate(groups):
         v = values[m]
@@ -82,11 +155,11 @@ def sufficient_stats(values, snr_db, snr_bins=(-5.0, 0.0, 5.0)):
 
 
 def stats_table(st, snr_bins=(-5.0, 0.0, 5.0), confidence=0.95):
-    """mean and t-CI half width per metric from all-reduced sufficient statistics."""
+    """mean and t-CI half width per metric from all-reduced sufficient statistics (three metrics, or four with ESTOI)."""
     import scipy.stats
     rows = {}
     for gi, name in enumerate(["all"] + ["snr=%g" % b for b in snr_bins]):
-        for k, key in enumerate(METRIC_KEYS):
+        for k, key in enumerate(METRIC_KEYS_ESTOI[:np.shape(st)[1]]):
             n, s1, s2 = st[gi, k]
             if n < 1:
                 continue

@@ -465,6 +465,70 @@ int vaenmf_spp_noise_given(const float* per, const float* spp_in, int64_t n, dou
 int vaenmf_gram3_batch(const float* s_hat, const float* s, const float* n, int32_t n_utt,
                        const int64_t* sample_offsets, double* out, void* stream);
 
+/* STOI (Taal et al. 2011) and ESTOI (Jensen & Taal 2016) -- replace pystoi's stoi(x, y, fs, extended) as the reference
+ * calls it (scripts/run_metrics_M1.py / run_metrics_M2.py:117, extended=True) for ragged batches of device signals at
+ * 10 kHz (another rate goes through vaenmf_resample_batch first).  clean x and processed y of one utterance have the same
+ * T samples.  Constants: frame 256, hop 128, FFT 512, 15 third-octave bands from 150 Hz, segments of N = 30 frames,
+ * beta = -15 dB, dynamic range 40 dB, EPS = 2^-52.  Everything below is float64 on the float32 samples.
+ *   window     w[i] = 0.5 - 0.5 cos(2 pi (i + 1) / 257), i = 0 .. 255: the symmetric Hann of 258 points without its two
+ *              zero ends (numpy.hanning(258)[1:-1]).
+ *   silence    frames start at 0, 128, .. < T - 256 (strictly: n_frames = ceil((T - 256) / 128) for T > 256, else 0; the
+ *              last full frame is dropped when 128 divides T - 256).  e_j = 20 log10(||w x[128 j : 128 j + 256]|| + EPS),
+ *              on the clean signal only; frame j is kept iff max_j e - 40 - e_j < 0.  k frames are kept, src[0 .. k-1]
+ *              their indices in order.  Both signals are rebuilt by overlap-adding their kept windowed frames at hop
+ *              128: sample 128 q + r (0 <= r < 128) is w[r] s[128 src[q] + r] (q <= k - 1) plus
+ *              w[r + 128] s[128 src[q-1] + r + 128] (q >= 1); the length is 128 (k - 1) + 256.
+ *   bands      frames of the rebuilt signals start at 0, 128, .. < length - 256: M = k - 1 frames, each windowed by w
+ *              again, zero-padded to 512 and transformed.  tob[m][b] = sqrt(sum of |.|^2 over the bins lo_b <= bin <
+ *              hi_b), lo_b / hi_b the bins of the grid 10000 i / 512 (i = 0 .. 256) nearest to 150 2^((2b-1)/6) and
+ *              150 2^((2b+1)/6) Hz (least squared distance, the first index on a tie).
+ *   segments   for m = 30 .. M the frames m-30 .. m-1 are one segment: J = M - 29 of them; with M < 30 the score is 1e-5
+ *              (the value pystoi returns with a warning).
+ *   ESTOI      in every segment and for both signals: each band row minus its mean over the 30 frames, divided by its
+ *              2-norm; then each frame column minus its mean over the 15 bands, divided by its 2-norm.
+ *              d = sum over the segments of sum(x_n y_n) / 30 / J.
+ *   STOI       per segment and band row: c = ||x|| / (||y|| + EPS), y' = min(c y, x (1 + 10^(15/20))); x and y' minus
+ *              their row means, each divided by (its norm + EPS); d = sum of x y' / (15 J).
+ * Deviations from pystoi, both on purpose:
+ *   - no dither.  pystoi adds EPS randn to the rows and columns it normalises, which makes the score of digital silence
+ *     a random number; here a row or column whose norm is exactly zero is scaled by 0 and nothing random is added
+ *     anywhere: the score is deterministic and that of an all-zero utterance is 0.
+ *   - the rate change.  pystoi resamples with an Octave-style filter of its own; the callers here use
+ *     vaenmf_resample_batch (scipy's default Kaiser filter).  On the reference's committed utterances the ESTOI of the
+ *     whole path rounds to the two decimals the reference printed.
+ *   Also: T <= 256 (no frame) gives 1e-5 and counts of zero, where pystoi raises on the maximum of an empty array.
+ * Per utterance the results are the same bits in any batch: no atomics, every sum in a fixed order by fixed lanes.  k, M
+ * and J stay on the device (no host synchronisation): the grids cover the worst case k = n_frames.
+ * vaenmf_stoi_geometry, HOST only: n_frames as above, max_spec_frames = max(n_frames - 1, 0) (M when every frame is
+ *   kept), max_segments = max(max_spec_frames - 29, 0); -1 for n_samples < 0 or more than 2^31 - 1 frames.
+ * vaenmf_stoi_bands, HOST only: lo, hi HOST int32 [15], the bin ranges above.
+ * vaenmf_stoi_work_bytes: the bytes of `work` for a batch with these sample_offsets (HOST int64 [n_utt+1], non-decreasing),
+ *   the same for the three calls below; -1 on bad arguments.
+ * Buffers of the three device calls: sample_offsets HOST int64 [n_utt+1]; clean, proc DEV float [sample_offsets[n_utt]],
+ *   utterance u at [sample_offsets[u], sample_offsets[u+1]), read only; keep DEV int32 [sum n_frames] (1 kept, 0 dropped,
+ *   utterances concatenated); counts DEV int32 [n_utt][3] = {n_frames, k, J}; tob_x, tob_y DEV double
+ *   [sum max_spec_frames][16]: row m < M of an utterance holds its 15 band magnitudes and a zero, rows >= M are neither
+ *   read nor written; d DEV double [n_utt]; work DEV, 8-byte aligned, work_bytes >= vaenmf_stoi_work_bytes (its contents
+ *   mean nothing between calls).  Every buffer has exactly the stated extent at its natural alignment (4 bytes for
+ *   float / int32, 8 for double); nothing is read or written outside them, and a buffer of extent zero may be null.
+ *   The offset tables the kernels need travel as kernel arguments; nothing is allocated except, at the first call on a
+ *   device, a table of 6 KiB (the window and the FFT twiddles, built in long double on the host; that call waits for
+ *   its upload), every later call only launches.  n_utt == 0 is a no-op.
+ * vaenmf_stoi_tob: silence removal and band magnitudes; writes keep, counts and rows < M of tob_x / tob_y.
+ * vaenmf_stoi_segments: d from tob_x / tob_y and counts as vaenmf_stoi_tob left them (a J larger than max_segments is
+ *   read as max_segments); extended != 0: ESTOI, else STOI.
+ * vaenmf_stoi_batch: both in one pass, the intermediates in `work`; counts may be null. */
+int vaenmf_stoi_geometry(int64_t n_samples, int32_t* n_frames, int32_t* max_spec_frames, int32_t* max_segments);
+int vaenmf_stoi_bands(int32_t* lo, int32_t* hi);
+int64_t vaenmf_stoi_work_bytes(int32_t n_utt, const int64_t* sample_offsets);
+int vaenmf_stoi_tob(const float* clean, const float* proc, int32_t n_utt, const int64_t* sample_offsets, int32_t* keep,
+                    int32_t* counts, double* tob_x, double* tob_y, void* work, int64_t work_bytes, void* stream);
+int vaenmf_stoi_segments(const double* tob_x, const double* tob_y, const int32_t* counts, int32_t n_utt,
+                         const int64_t* sample_offsets, int32_t extended, double* d, void* work, int64_t work_bytes,
+                         void* stream);
+int vaenmf_stoi_batch(const float* clean, const float* proc, int32_t n_utt, const int64_t* sample_offsets, int32_t extended,
+                      double* d, int32_t* counts, void* work, int64_t work_bytes, void* stream);
+
 /* Per-kernel device timing with HIP events recorded on the launch stream around every
  * hot-path launch (kinds: 0 mh_chain, 1 decode+W-statistics, 2 W update, 3 decode+H/g/cost,
  * 4 decode+Wiener).  enable(max_launches>0) pre-creates the events (no allocation at
