@@ -79,6 +79,10 @@ SIGNATURES = {
     "vaenmf_stoi_tob": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "vaenmf_stoi_segments": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _I64, _P]),
     "vaenmf_stoi_batch": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _I64, _P]),
+    "vaenmf_mix_work_bytes": (_I64, [_I]),
+    "vaenmf_mix_batch": (_I, [_P, _I, _P, _P, _P, _I64, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "vaenmf_moments_work_bytes": (_I64, [_I64, _I]),
+    "vaenmf_feature_moments": (_I, [_P, _I64, _I, _I, _I, _P, _P, _P, _I64, _P]),
     "vaenmf_profile_enable": (_I, [_P, _I]),
     "vaenmf_profile_read": (_I, [_P, _P, _P]),
     "vaenmf_wchain_addressable": (_I, [_I64, _I, _I, _I, _I, _I, _I]),

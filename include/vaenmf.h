@@ -529,6 +529,55 @@ int vaenmf_stoi_segments(const double* tob_x, const double* tob_y, const int32_t
 int vaenmf_stoi_batch(const float* clean, const float* proc, int32_t n_utt, const int64_t* sample_offsets, int32_t extended,
                       double* d, int32_t* counts, void* work, int64_t work_bytes, void* stream);
 
+/* Noisy data sets -- the arithmetic of the reference's scripts/create_test_set.py:80-103 (process_save_utt) and
+ * scripts/create_noisy_train_set.py:219-250, 299-303 for ragged batches of device signals: mixing speech with noise at a
+ * signal-to-noise ratio, and the per-bin running sums behind trainset_mean.npy / trainset_std.npy.
+ *
+ * vaenmf_mix_batch.  Utterance u has the speech row a[0 .. T) (T = in_offsets[u+1] - in_offsets[u]), a cut c = cuts[u] of
+ *   samples dropped at its start (the reference drops int(0.1 fs)), a start b = starts[u] into the ONE noise buffer of
+ *   noise_len samples that the batch shares, and a factor f = factors[u] = 10^(-snr_db / 10) computed by the caller.  With
+ *   T' = T - c, everything in float64 on the float32 samples:
+ *     p   = max |a[i]| over i >= c                                     (speech[int(0.1 fs):]; speech / max|speech|)
+ *     s_i = a[i + c] / p,   v_i = noise[b + i],   i in [0, T')
+ *     Es  = sum s_i^2,  En = sum v_i^2,  k = Es f / En,  n_i = sqrt(k) v_i,  x_i = s_i + n_i
+ *     joint_norm != 0 (create_test_set.py:99-103):       m = max_i max(|s_i|, |n_i|, |x_i|);  s_i / m, n_i / m, x_i / m
+ *     joint_norm == 0 (create_noisy_train_set.py:244):   m = 1
+ *   s, n, x receive the three signals, each rounded ONCE from its float64 value to float32, utterance u at
+ *   [out_offsets[u], out_offsets[u+1]), which must span exactly T' samples; stats[u] = {p, Es, En, k, m}.
+ *   Determinism: the samples of an utterance are cut into min(16, ceil(T' / 4096)) consecutive spans of equal length, one
+ *   workgroup each -- a function of T' alone -- every workgroup sums in a fixed order and leaves one partial, and the
+ *   partials are combined in span order; no atomics.  An utterance therefore has the same bits in s, n, x and stats alone,
+ *   in any batch and in every run.  Multiplying the speech, or the noise, by a power of two changes no bit of s, n, x
+ *   (short of underflow).
+ *   Degenerate utterances: p == 0 (silent speech), En == 0 (silent noise segment) or a k that is not finite give zeros in
+ *   that utterance's s, n, x and stats {p, Es, En, 0, 0}; no NaN or Inf is written.  k == 0 is how a caller tells.
+ *   Refused with -1 before any launch (nothing is written; the message names the utterance): T' < 1, c < 0, b < 0,
+ *   b + T' > noise_len, an out_offsets span other than T', a factor that is not positive and finite.
+ *   Buffers: speech DEV float [in_offsets[n_utt]], noise DEV float [noise_len], s, n, x DEV float [out_offsets[n_utt]], all
+ *   at their natural (4-byte) alignment and read / written one float at a time: nothing is read outside [c, T) of a speech
+ *   row and [b, b + T') of the noise, nothing written outside an utterance's output span.  in_offsets, out_offsets HOST
+ *   int64 [n_utt+1]; cuts, starts HOST int64 [n_utt]; factors HOST double [n_utt]; stats DEV double [n_utt][5], 8-byte
+ *   aligned; work DEV, 8-byte aligned, work_bytes >= vaenmf_mix_work_bytes(n_utt) (its contents mean nothing between
+ *   calls).  The tables travel as kernel arguments: no allocation, no copy, no synchronisation.  n_utt == 0 is a no-op.
+ * vaenmf_mix_work_bytes: 552 n_utt, or -1 for n_utt outside [0, 2^24].
+ *
+ * vaenmf_feature_moments.  P DEV float [n_frames][ld], frame-major; bins f < F are read, columns F .. ld-1 may hold
+ *   anything.  S1[f] = sum_t (double)P[t][f], S2[f] = sum_t ((double)P[t][f])^2 (create_noisy_train_set.py:302-303, which
+ *   keeps these sums in float32), S1, S2 DEV double [F], 8-byte aligned.  accumulate == 0 overwrites S1 / S2; accumulate
+ *   != 0 adds the call's sums onto their contents with exactly one float64 addition per bin, so a set can be streamed batch
+ *   by batch.  The frames are cut into min(256, ceil(n_frames / 64)) spans of equal length -- a function of n_frames alone --
+ *   each summed in a fixed order, and the spans' partials are added in span order: the same bits in every run.  n_frames
+ *   == 0 leaves S1 / S2 alone (accumulate) or zeroes them.  work DEV, 8-byte aligned, work_bytes >=
+ *   vaenmf_moments_work_bytes(n_frames, F).  -1 for n_frames < 0, F < 1 or ld < F.  No allocation, no synchronisation. */
+int64_t vaenmf_mix_work_bytes(int32_t n_utt);
+int vaenmf_mix_batch(const float* speech, int32_t n_utt, const int64_t* in_offsets, const int64_t* cuts, const float* noise,
+                     int64_t noise_len, const int64_t* starts, const double* factors, int32_t joint_norm,
+                     const int64_t* out_offsets, float* s, float* n, float* x, double* stats, void* work, int64_t work_bytes,
+                     void* stream);
+int64_t vaenmf_moments_work_bytes(int64_t n_frames, int32_t F);
+int vaenmf_feature_moments(const float* P, int64_t n_frames, int32_t F, int32_t ld, int32_t accumulate, double* S1, double* S2,
+                           void* work, int64_t work_bytes, void* stream);
+
 /* Per-kernel device timing with HIP events recorded on the launch stream around every
  * hot-path launch (kinds: 0 mh_chain, 1 decode+W-statistics, 2 W update, 3 decode+H/g/cost,
  * 4 decode+Wiener).  enable(max_launches>0) pre-creates the events (no allocation at
