@@ -5,3 +5,4 @@ from .mcem import MCEM_M1, MCEM_M2, EM_noNMF, MCEM_M2_noNMF
 from .engine import BatchEngine
 from .resample import resample, resample_batch
 from .dataset import FeatureMoments, make_test_set, make_train_set, mix_batch, plan_mixes
+from .train import Trainer, fit_classifier, fit_m1, fit_m2

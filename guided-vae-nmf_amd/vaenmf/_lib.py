@@ -9,7 +9,9 @@ LIB_PATH = os.environ.get("VAENMF_LIB") or os.path.join(_HERE, "libvaenmf.so")  
 PREC_BF16X3, PREC_BF16 = 0, 1
 RNG_REPLAY, RNG_DEVICE = 0, 1
 Q_FS, Q_KP, Q_TILES, Q_NT, Q_NUTT, Q_MSTEP_PATH, Q_WTILES, Q_EM_GRAPH, Q_DEV_ALLOCS, Q_W_FUSED, Q_CHAIN_KERNEL, Q_LP, Q_STORE_ALIGNED = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12
-ACT_NONE, ACT_TANH, ACT_RELU, ACT_SIGMOID, ACT_STEP = 0, 1, 2, 3, 4
+ACT_NONE, ACT_TANH, ACT_RELU, ACT_SIGMOID, ACT_STEP, ACT_EXP = 0, 1, 2, 3, 4, 5
+TRAIN_M1, TRAIN_M2, TRAIN_CLASSIFIER = 0, 1, 2
+TRAIN_PARAM, TRAIN_GRAD, TRAIN_ADAM_M, TRAIN_ADAM_V = 0, 1, 2, 3
 LABEL_IBM, LABEL_VAD = 0, 1
 
 
@@ -28,6 +30,12 @@ PAD_REFLECT, PAD_CONSTANT = 0, 1
 class StftOpts(C.Structure):
     _fields_ = [("nfft", C.c_int32), ("hop", C.c_int32), ("center", C.c_int32), ("pad_mode", C.c_int32),
                 ("window", C.c_void_p)]
+
+
+class TrainerConfig(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("x_dim", C.c_int32), ("y_dim", C.c_int32), ("z_dim", C.c_int32), ("n_hidden", C.c_int32),
+                ("hidden", C.c_int32 * 2), ("max_batch", C.c_int32), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("adam_eps", C.c_double), ("loss_eps", C.c_double)]
 
 
 # name -> (restype, argtypes); every symbol include/vaenmf.h declares
@@ -83,6 +91,31 @@ SIGNATURES = {
     "vaenmf_mix_batch": (_I, [_P, _I, _P, _P, _P, _I64, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "vaenmf_moments_work_bytes": (_I64, [_I64, _I]),
     "vaenmf_feature_moments": (_I, [_P, _I64, _I, _I, _I, _P, _P, _P, _I64, _P]),
+    "vaenmf_train_dense_fwd": (_I, [_P, _I, _I, _I, _P, _I, _P, _I, _I, _P, _I, _P]),
+    "vaenmf_train_dense_dx": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P, _I, _P]),
+    "vaenmf_train_dense_dw": (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _I, _P, _P]),
+    "vaenmf_elbo_out": (_I, [_P, _I, _P, _I, _I, _I, _D, _P, _I, _P, _P]),
+    "vaenmf_elbo_latent_fwd": (_I, [_P, _I, _P, _I, _I, _P, _I, _P]),
+    "vaenmf_elbo_latent_bwd": (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _I, _P, _P]),
+    "vaenmf_bce_head": (_I, [_P, _I, _P, _I, _I, _I, _D, _P, _I, _P, _P, _P]),
+    "vaenmf_loss_reduce": (_I, [_P, _P, _P, _I, _P, _P]),
+    "vaenmf_train_gather": (_I, [_P, _I, _I64, _P, _I, _I, _P, _P, _F, _P, _I, _I, _P]),
+    "vaenmf_adam": (_I, [_P, _P, _P, _P, _I64, _I64, _D, _D, _D, _D, _P]),
+    "vaenmf_train_eps_fill": (_I, [C.c_uint64, _I64, _I, _I, _P, _P]),
+    "vaenmf_trainer_create": (_I, [C.POINTER(TrainerConfig), C.POINTER(_P)]),
+    "vaenmf_trainer_destroy": (None, [_P]),
+    "vaenmf_trainer_num_tensors": (_I, [_P]),
+    "vaenmf_trainer_tensor_shape": (_I, [_P, _I, C.POINTER(_I), C.POINTER(_I)]),
+    "vaenmf_trainer_set_tensor": (_I, [_P, _I, _I, _P, _P]),
+    "vaenmf_trainer_get_tensor": (_I, [_P, _I, _I, _P, _P]),
+    "vaenmf_trainer_set_params": (_I, [_P, _I, _P, _P]),
+    "vaenmf_trainer_get_params": (_I, [_P, _I, _P, _P]),
+    "vaenmf_trainer_set_norm": (_I, [_P, _P, _P, _F]),
+    "vaenmf_trainer_step_count": (_I64, [_P]),
+    "vaenmf_trainer_set_step_count": (_I, [_P, _I64]),
+    "vaenmf_trainer_step": (_I, [_P, _P, _I, _P, _I, _I64, _P, _I, _P, C.c_uint64, _P, _P]),
+    "vaenmf_trainer_eval": (_I, [_P, _P, _I, _P, _I, _I64, _P, _I, _P, C.c_uint64, _P, _P]),
+    "vaenmf_trainer_eps_fill": (_I, [_P, _I64, _I, C.c_uint64, _P, _P]),
     "vaenmf_profile_enable": (_I, [_P, _I]),
     "vaenmf_profile_read": (_I, [_P, _P, _P]),
     "vaenmf_wchain_addressable": (_I, [_I64, _I, _I, _I, _I, _I, _I]),

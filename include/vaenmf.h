@@ -117,7 +117,8 @@ enum { VAENMF_Q_FS = 0, VAENMF_Q_KP = 1, VAENMF_Q_TILES = 2, VAENMF_Q_NT = 3, VA
                                     reuses a plan can check that a call allocated nothing */
 
 enum { VAENMF_ACT_NONE = 0, VAENMF_ACT_TANH = 1, VAENMF_ACT_RELU = 2, VAENMF_ACT_SIGMOID = 3,
-       VAENMF_ACT_STEP = 4 };   /* 1 if x > 0 else 0: sigmoid(x) > 0.5, scripts/evaluate_M2_vad.py:131 */
+       VAENMF_ACT_STEP = 4,     /* 1 if x > 0 else 0: sigmoid(x) > 0.5, scripts/evaluate_M2_vad.py:131 */
+       VAENMF_ACT_EXP = 5 };    /* the training layers only (vaenmf_train_dense_*): the decoder's output, models.py:133 */
 
 typedef struct {
   int32_t F;          /* frequency bins, n_fft/2+1: any value in 1..640 (n_fft need not be a power of two; padding bins
@@ -577,6 +578,110 @@ int vaenmf_mix_batch(const float* speech, int32_t n_utt, const int64_t* in_offse
 int64_t vaenmf_moments_work_bytes(int64_t n_frames, int32_t F);
 int vaenmf_feature_moments(const float* P, int64_t n_frames, int32_t F, int32_t ld, int32_t accumulate, double* S1, double* S2,
                            void* work, int64_t work_bytes, void* stream);
+
+/* ---- Training (scripts/training_M1.py, training_M2.py, training_classifier.py) ---------------------------------------
+ * All arithmetic is fp32 with fp32 accumulation, loss sums are double.  Nothing here allocates, copies to the host or
+ * synchronises except vaenmf_trainer_create / _destroy; every call is a few launches on `stream`.  The same inputs give the
+ * same bits in every run: no atomics, no split reductions.
+ *
+ * Dense layers on v_mfma_f32_16x16x4_f32: every output element is the sum of four chains c_j = fmaf(a_k, b_k, c_j) over
+ * the k with (k / 4) % 4 == j, ascending, each from 0, and of the bias: (c0 + c1), (c2 + c3), their sum and the bias are
+ * added by fp32 two-sums, and the four rounding errors ((e01 + e23) + e) + eb are added to the result once.
+ * Rows carry leading dimensions; columns between a row's width and its leading dimension are never read and never written.
+ *   vaenmf_train_dense_fwd  Y[M][out] = act(X[M][in] W[out][in]^T + b), act one of NONE, TANH, RELU, SIGMOID, EXP; b may be
+ *                           NULL (no bias).  W rows are ldw apart.
+ *   vaenmf_train_dense_dx   dX[M][in] = (dZ[M][out] W[out][in]) * act'(Yprev[M][in]), the derivative of the PREVIOUS layer's
+ *                           activation from its saved output: tanh 1 - y^2, relu y > 0, exp y, sigmoid y (1 - y), NONE 1
+ *                           (Yprev may then be NULL).  `in` may be fewer than W's columns: the first `in` are used.
+ *   vaenmf_train_dense_dw   dW[out][in] = dZ[M][out]^T X[M][in]; db[out] = column sums of dZ from the same pass (NULL: not
+ *                           wanted).  The reduction is the batch M, walked by one workgroup per tile in row order.
+ *   Refused with -1: M outside [1, 65536], in / out outside [1, 4096], a leading dimension below its width.
+ *
+ * Heads.  B rows, one workgroup (or wavefront) per row; the per-row sums are double.
+ *   vaenmf_elbo_out         a = the decoder's output BEFORE the exponential, r = exp(a) (utils.py:66-69):
+ *                           row_recon[b] = sum_f (x / r - log(x + eps) + a - 1), dA[b][f] = (1 - x / r) / B (NULL: no gradient).
+ *   vaenmf_elbo_latent_fwd  ML[b] = [mu (z) | logvar (z)]; Z[b][j] = mu + exp(logvar / 2) eps[b][j], j < z (eps DEV [B][z]).
+ *   vaenmf_elbo_latent_bwd  row_kl[b] = -1/2 sum_j (logvar - mu^2 - exp(logvar)); with dML: dML[b] = [dmu | dlogvar],
+ *                           dmu = mu / B + dz, dlogvar = (exp(logvar) - 1) / (2 B) + dz exp(logvar / 2) eps / 2.
+ *   vaenmf_bce_head         a = the classifier's output BEFORE the sigmoid, yh = sigmoid(a), evaluated in double with
+ *                           1 - yh = sigmoid(-a) (utils.py:55-56): row_loss[b] = -sum_j (y log(yh + eps) + (1 - y) log(1 - yh + eps)),
+ *                           dA = -(y / (yh + eps) - (1 - y) / (1 - yh + eps)) yh (1 - yh) / B,
+ *                           row_cnt[b] = {tp, tn, fp, fn} of (yh > 0.5) against (y > 0.5) (training_classifier.py:148-154).
+ *   vaenmf_loss_reduce      out (DEV, 64 bytes, 8-byte aligned): double {a + b, a, b, 0} with a = sum(row_a) / B, b =
+ *                           sum(row_b) / B (row_b NULL: 0), then int64 {tp, tn, fp, fn} summed over row_cnt (NULL: zeros).
+ * vaenmf_train_gather: dst[b][col0 + c] = src[idx[b]][c] for c < ncol, or (src - mean[c]) / (std[c] + eps) when mean / std
+ *   (DEV [ncol]) are given (training_classifier.py:133-135).  idx DEV int32 [B], each in [0, NT); a row outside is not read
+ *   and yields NaN.
+ * vaenmf_adam: torch.optim.Adam's default update (no weight decay, no amsgrad) of n parameters in one launch, `step` = 1 for
+ *   the first: m += (1 - beta1) (g - m); v = beta2 v + (1 - beta2) g g; p += (-(lr / (1 - beta1^step)) m) / (sqrt(v) /
+ *   sqrt(1 - beta2^step) + eps), the bias corrections computed on the host in double.
+ * vaenmf_train_eps_fill: the N(0,1) draws [B][z] of training step `step` (>= 1) under `seed`: the generator of the MH
+ *   chains (z / 4 streams of four per row), keyed by (seed, step, row).  z a multiple of 4. */
+int vaenmf_train_dense_fwd(const float* X, int32_t M, int32_t in, int32_t ldx, const float* W, int32_t ldw, const float* b,
+                           int32_t out, int32_t act, float* Y, int32_t ldy, void* stream);
+int vaenmf_train_dense_dx(const float* dZ, int32_t M, int32_t out, int32_t ldz, const float* W, int32_t ldw, int32_t in,
+                          const float* Yprev, int32_t ldp, int32_t act, float* dX, int32_t lddx, void* stream);
+int vaenmf_train_dense_dw(const float* dZ, int32_t M, int32_t out, int32_t ldz, const float* X, int32_t in, int32_t ldx,
+                          float* dW, int32_t lddw, float* db, void* stream);
+int vaenmf_elbo_out(const float* X, int32_t ldx, const float* A, int32_t lda, int32_t B, int32_t F, double eps, float* dA,
+                    int32_t ldd, double* row_recon, void* stream);
+int vaenmf_elbo_latent_fwd(const float* ML, int32_t ldm, const float* eps, int32_t B, int32_t z, float* Z, int32_t ldz, void* stream);
+int vaenmf_elbo_latent_bwd(const float* ML, int32_t ldm, const float* eps, const float* dZ, int32_t lddz, int32_t B, int32_t z,
+                           float* dML, int32_t lddm, double* row_kl, void* stream);
+int vaenmf_bce_head(const float* A, int32_t lda, const float* Y, int32_t ldy, int32_t B, int32_t D, double eps, float* dA, int32_t ldd,
+                    double* row_loss, int32_t* row_cnt, void* stream);
+int vaenmf_loss_reduce(const double* row_a, const double* row_b, const int32_t* row_cnt, int32_t B, double* out, void* stream);
+int vaenmf_train_gather(const float* src, int32_t lds, int64_t NT, const int32_t* idx, int32_t B, int32_t ncol, const float* mean,
+                        const float* std, float eps, float* dst, int32_t ldd, int32_t col0, void* stream);
+int vaenmf_adam(float* p, const float* g, float* m, float* v, int64_t n, int64_t step, double lr, double beta1, double beta2,
+                double eps, void* stream);
+int vaenmf_train_eps_fill(uint64_t seed, int64_t step, int32_t B, int32_t z, float* eps_out, void* stream);
+
+/* The trainer: a model's parameters, gradients and Adam state in one device arena, and the buffers of a step.
+ *   kind M1: encoder x -> hidden (tanh) -> [mu | logvar], decoder z -> reversed(hidden) (tanh) -> exp (models.py:90-133);
+ *   M2: the same over [x | y] and [z | y] (models.py:184-197); CLASSIFIER: x -> hidden (relu) -> sigmoid, y_dim outputs
+ *   (models.py:41-62, batch_norm = False).  One or two hidden layers of any width in [1, 4096]; x_dim, y_dim in [1, 4096]
+ *   with x_dim + y_dim <= 4096 (M1: y_dim = 0); z_dim a multiple of 4 in [4, 1024]; max_batch in [1, 65536].  Anything
+ *   else is refused with -1 and a message.
+ * Tensors are numbered in the order of the reference's state_dict (weight [out][in] then bias of every layer: encoder
+ *   hidden layers, mu, log_var, decoder hidden layers, reconstruction; classifier: hidden layers, output_layer);
+ *   vaenmf_trainer_tensor_shape gives rows and cols (cols = 0 for a bias).  set / get copy one tensor (src / dst DEV or
+ *   HOST, contiguous) asynchronously on `stream`; `which` selects parameters, the gradients of the last step, or Adam's m / v.
+ * vaenmf_trainer_step: one step on the rows idx[0..B) (DEV int32) of X DEV [NT][ldx] (and Y DEV [NT][ldy]; M1: NULL):
+ *   gather, forward, loss, backward, Adam.  eps DEV [B][z_dim] replays the reparameterisation draws; NULL draws them on the
+ *   device, keyed by (seed, the step's number, row) -- the draws vaenmf_trainer_eps_fill(t, step number, ..) returns, the
+ *   first step's number being vaenmf_trainer_step_count() + 1 = 1.  losses DEV, 64 bytes as vaenmf_loss_reduce writes them:
+ *   {loss, recon, KL} (classifier: {loss, loss, 0}) and {tp, tn, fp, fn} (VAEs: zeros).  Means are over B.
+ * vaenmf_trainer_eval: forward and loss only; parameters, gradients, Adam state and the step count stay as they are.
+ * vaenmf_trainer_set_norm: the classifier's input becomes (x - mean) / (std + eps); mean, std DEV [x_dim], caller-owned,
+ *   read at every step (NULL, NULL: no normalisation). */
+typedef struct vaenmf_trainer vaenmf_trainer;
+enum { VAENMF_TRAIN_M1 = 0, VAENMF_TRAIN_M2 = 1, VAENMF_TRAIN_CLASSIFIER = 2 };
+enum { VAENMF_TRAIN_PARAM = 0, VAENMF_TRAIN_GRAD = 1, VAENMF_TRAIN_ADAM_M = 2, VAENMF_TRAIN_ADAM_V = 3 };
+typedef struct {
+  int32_t kind;                  /* VAENMF_TRAIN_* */
+  int32_t x_dim, y_dim, z_dim;
+  int32_t n_hidden, hidden[2];   /* h_dim as the reference's constructors take it */
+  int32_t max_batch;
+  double lr, beta1, beta2, adam_eps;   /* torch.optim.Adam(lr, betas, eps) */
+  double loss_eps;               /* eps of elbo / binary_cross_entropy (the scripts: 1e-8) */
+} vaenmf_trainer_config;
+int vaenmf_trainer_create(const vaenmf_trainer_config* cfg, vaenmf_trainer** out);
+void vaenmf_trainer_destroy(vaenmf_trainer* t);
+int vaenmf_trainer_num_tensors(const vaenmf_trainer* t);
+int vaenmf_trainer_tensor_shape(const vaenmf_trainer* t, int32_t i, int32_t* rows, int32_t* cols);
+int vaenmf_trainer_set_tensor(vaenmf_trainer* t, int32_t which, int32_t i, const float* src, void* stream);
+int vaenmf_trainer_get_tensor(const vaenmf_trainer* t, int32_t which, int32_t i, float* dst, void* stream);
+int vaenmf_trainer_set_params(vaenmf_trainer* t, int32_t i, const float* src, void* stream);
+int vaenmf_trainer_get_params(const vaenmf_trainer* t, int32_t i, float* dst, void* stream);
+int vaenmf_trainer_set_norm(vaenmf_trainer* t, const float* mean, const float* std, float eps);
+int64_t vaenmf_trainer_step_count(const vaenmf_trainer* t);
+int vaenmf_trainer_set_step_count(vaenmf_trainer* t, int64_t step);
+int vaenmf_trainer_step(vaenmf_trainer* t, const float* X, int32_t ldx, const float* Y, int32_t ldy, int64_t NT, const int32_t* idx,
+                        int32_t B, const float* eps, uint64_t seed, double* losses, void* stream);
+int vaenmf_trainer_eval(vaenmf_trainer* t, const float* X, int32_t ldx, const float* Y, int32_t ldy, int64_t NT, const int32_t* idx,
+                        int32_t B, const float* eps, uint64_t seed, double* losses, void* stream);
+int vaenmf_trainer_eps_fill(const vaenmf_trainer* t, int64_t step, int32_t B, uint64_t seed, float* eps_out, void* stream);
 
 /* Per-kernel device timing with HIP events recorded on the launch stream around every
  * hot-path launch (kinds: 0 mh_chain, 1 decode+W-statistics, 2 W update, 3 decode+H/g/cost,
