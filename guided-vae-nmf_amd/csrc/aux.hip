@@ -315,6 +315,24 @@ __global__ __launch_bounds__(256) void hbm_read_probe_kernel(const u32x4p* __res
   if (acc == 0x9E3779B9u) sink[0] = acc;
 }
 
+// Wavefront-sum probe (tests): one wavefront per set of 4 x 64 floats.  Every lane writes what it holds of the four totals
+// taken one at a time (sum_rows4 of sum_row16, as wave_sum of stream.hip), of the four through one shared cross-row stage
+// (sum_rows4_x4: row j = total j) and of two pairs (sum_rows4_x2: rows 0 and 2 = the first, rows 1 and 3 = the second).
+__global__ __launch_bounds__(64) void wave_sum_probe_kernel(const float* __restrict__ x, float* one, float* x4, float* x2) {
+  const size_t set = blockIdx.x;
+  const int lane = threadIdx.x;
+  float v[4], r[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    v[q] = x[(set * 4 + q) * 64 + lane];
+    r[q] = sum_row16(v[q]);
+    one[(set * 4 + q) * 64 + lane] = sum_rows4(r[q]);
+  }
+  x4[set * 64 + lane] = sum_rows4_x4(r[0], r[1], r[2], r[3]);
+  x2[(set * 2 + 0) * 64 + lane] = sum_rows4_x2(r[0], r[1]);
+  x2[(set * 2 + 1) * 64 + lane] = sum_rows4_x2(r[2], r[3]);
+}
+
 }  // namespace
 
 int vn_launch_w_update(const vaenmf_plan* p, float* W, const float* Ht, hipStream_t st) {
@@ -415,5 +433,16 @@ extern "C" int vaenmf_hbm_read_probe(const void* buf, int64_t bytes, int32_t rep
   VN_CHECK_HIP(e);
   VN_CHECK_HIP(hipGetLastError());
   *gbps_out = (double)(n16 * 16) * reps / ((double)ms * 1e-3) / 1e9;
+  return 0;
+}
+
+// Test aid (not on the hot path): the wavefront sums of common.h on n sets of 4 x 64 floats, x DEV [n][4][64].  Written per
+// lane: one DEV [n][4][64] each value summed on its own (sum_rows4 of sum_row16), x4 DEV [n][64] the four through
+// sum_rows4_x4 (lanes 16 j .. 16 j + 15 hold total j), x2 DEV [n][2][64] the pairs (0, 1) and (2, 3) through sum_rows4_x2
+// (lanes 0-15 and 32-47 hold the pair's first total, lanes 16-31 and 48-63 its second).
+extern "C" int vaenmf_wave_sum_probe(const float* x, int32_t n, float* one, float* x4, float* x2, void* stream) {
+  VN_REQUIRE(x && one && x4 && x2 && n > 0, "vaenmf_wave_sum_probe: bad arguments");
+  hipLaunchKernelGGL(wave_sum_probe_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, x, one, x4, x2);
+  VN_CHECK_HIP(hipGetLastError());
   return 0;
 }

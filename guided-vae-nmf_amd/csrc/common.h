@@ -300,6 +300,29 @@ __device__ __forceinline__ float swap32_add(float v) {      // v[l] + v[l ^ 32]
   return __builtin_bit_cast(float, x) + __builtin_bit_cast(float, y);
 }
 __device__ __forceinline__ float sum_rows4(float v) { return swap32_add(swap16_add(v)); }   // sum over q
+// Several sums over q at once: the swaps are fed two DIFFERENT values, so neither half of an exchange is thrown away and no
+// opaque copy is needed.  With r0..r3 the four rows of a register,
+//   v_permlane16_swap(a, b) leaves [a0 b0 a2 b2] and [a1 b1 a3 b3]; their sum is [a0+a1, b0+b1, a2+a3, b2+b3]
+//   v_permlane32_swap(s, t) leaves [s0 s1 t0 t1] and [s2 s3 t2 t3]; their sum is [s0+s2, s1+s3, t0+t2, t1+t3]
+// Every total is (r0 + r1) + (r2 + r3), the tree of sum_rows4: the same bits.
+__device__ __forceinline__ float swap16_add2(float a, float b) {
+  auto r = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), false, false);
+  unsigned x = r[0], y = r[1];
+  asm volatile("" : "+v"(x), "+v"(y));      // (as in swap16_add: r[0] + r[0] is emitted otherwise, with different operands too)
+  return __builtin_bit_cast(float, x) + __builtin_bit_cast(float, y);
+}
+__device__ __forceinline__ float swap32_add2(float s, float t) {
+  auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, s), __builtin_bit_cast(unsigned, t), false, false);
+  unsigned x = r[0], y = r[1];
+  asm volatile("" : "+v"(x), "+v"(y));
+  return __builtin_bit_cast(float, x) + __builtin_bit_cast(float, y);
+}
+// rows 0 and 2 (lanes 0-15, 32-47) hold the sum over q of a, rows 1 and 3 (lanes 16-31, 48-63) that of b
+__device__ __forceinline__ float sum_rows4_x2(float a, float b) { return swap32_add(swap16_add2(a, b)); }
+// row j (lanes 16 j .. 16 j + 15) holds the sum over q of the j-th argument
+__device__ __forceinline__ float sum_rows4_x4(float a, float b, float c, float d) {
+  return swap32_add2(swap16_add2(a, b), swap16_add2(c, d));
+}
 __device__ __forceinline__ double swap16_add_d(double v) {
   const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
   const unsigned lo = (unsigned)b, hi = (unsigned)(b >> 32);

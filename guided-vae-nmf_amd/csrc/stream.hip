@@ -63,11 +63,19 @@ struct StreamArgs {
 };
 
 __device__ __forceinline__ float wave_sum(float v) { return sum_rows4(sum_row16(v)); }
+// two wavefront sums that share the cross-row stage: the sum of a in lane 0, that of b in lane 16 (sum_rows4_x2, common.h)
+__device__ __forceinline__ float wave_sum2(float a, float b) { return sum_rows4_x2(sum_row16(a), sum_row16(b)); }
 // a value every lane holds alike, kept in a scalar register from here on
 __device__ __forceinline__ float vn_uniform(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); }
 // lane l's value of v as a wave-uniform scalar (l: compile time or uniform).  v by reference: by value, the copy the
 // bit cast then reads changes the instruction order of the kernels that use it.
 __device__ __forceinline__ float read_lane(const float& v, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)); }
+// sa = wave_sum(a), sb = wave_sum(b) through the shared cross-row stage, as wave-uniform scalars (the same bits)
+__device__ __forceinline__ void wave_sum_pair(float a, float b, float& sa, float& sb) {
+  const float s2 = wave_sum2(a, b);
+  sa = read_lane(s2, 0);
+  sb = read_lane(s2, 16);
+}
 
 template <int NCH, int KP, typename ST, bool TAIL = false>
 struct FrameCtx {
@@ -183,6 +191,12 @@ struct FrameCtx {
 #pragma unroll
     for (int j = 0; j < 4; ++j) wl[(k + j) * a.Fs + f] = v[j];
   }
+  // this lane's four bins of rank k in chunk c.  Rank <= 8: at bin fo, i.e. bin 0 for a lane without real bins in the chunk,
+  // which w_dot4_ reads without a branch -- one set of addresses for every reader (they are loop-invariant vector registers)
+  __device__ __forceinline__ const f32x4* lds_row(int k, int c) const {
+    if constexpr (KP <= 8) return reinterpret_cast<const f32x4*>(wl + k * a.Fs + fo[c]);
+    else return reinterpret_cast<const f32x4*>(wl + k * a.Fs + f0[c]);
+  }
   __device__ __forceinline__ const float* w_row(int utt, int f) const {   // global layout only
     return a.W + ((size_t)utt * a.Fs + f) * KP;
   }
@@ -195,7 +209,7 @@ struct FrameCtx {
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         if (cv[c]) {
 #pragma unroll
-          for (int k = 0; k < KP; ++k) v += *reinterpret_cast<const f32x4*>(wl + k * a.Fs + f0[c]) * h[k];
+          for (int k = 0; k < KP; ++k) v += *lds_row(k, c) * h[k];
         }
         vb[c] = cv[c] ? v : f32x4{1.f, 1.f, 1.f, 1.f};
       }
@@ -251,7 +265,7 @@ struct FrameCtx {
     for (int c = 0; c < NCH; ++c)
       if (cv[c]) {
         if (L) {
-          const f32x4 w4 = *reinterpret_cast<const f32x4*>(wl + k * a.Fs + f0[c]);
+          const f32x4 w4 = *lds_row(k, c);
 #pragma unroll
           for (int t = 0; t < 4; ++t) { nu += w4[t] * P[c][t]; de += w4[t] * A[c][t]; }
         } else {
@@ -273,6 +287,42 @@ struct FrameCtx {
                                         float& nu, float& de) const {
     if (WPRIV || in_lds) w_dot_<true>(utt, k, P, A, px, ax, nu, de);
     else w_dot_<false>(utt, k, P, A, px, ax, nu, de);
+  }
+  // The same for the four ranks k0 .. k0+3 at once, per rank the products of w_dot_ in its order, and no lane or rank left
+  // out by a branch: a lane without real bins in chunk c carries P = A = 0 there and reads the rows of bin 0 (fo), the lanes
+  // other than the leading one carry px = ax = 0, as every lane does without an extra bin (wx = 0 then), and the padded ranks
+  // have zero columns of W.  Each of those terms is +0, which leaves a sum of non-negative terms as it is.
+  template <bool L>
+  __device__ __forceinline__ void w_dot4_(int utt, int k0, const f32x4 (&P)[NCH], const f32x4 (&A)[NCH], float px, float ax,
+                                          float (&nu)[4], float (&de)[4]) const {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) nu[j] = de[j] = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      f32x4 w4[4];        // L: [rank][bin]; global rows: [bin][rank]
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        w4[j] = L ? *lds_row(k0 + j, c) : *reinterpret_cast<const f32x4*>(w_row(utt, (int)fo[c] + j) + k0);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const float w = L ? w4[j][t] : w4[t][j];
+          nu[j] += w * P[c][t];
+          de[j] += w * A[c][t];
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float w = wxk(k0 + j);
+      nu[j] += w * px;
+      de[j] += w * ax;
+    }
+  }
+  __device__ __forceinline__ void w_dot4(int utt, int k0, const f32x4 (&P)[NCH], const f32x4 (&A)[NCH], float px, float ax,
+                                         float (&nu)[4], float (&de)[4]) const {
+    if (WPRIV || in_lds) w_dot4_<true>(utt, k0, P, A, px, ax, nu, de);
+    else w_dot4_<false>(utt, k0, P, A, px, ax, nu, de);
   }
   __device__ __forceinline__ void ext_var(int n, f32x4 (&vb)[NCH], float& vbx) const {   // caller-given Vb (noNMF)
     const float* row = a.Vb + (size_t)n * a.Fs;
@@ -332,11 +382,15 @@ struct RowBatch {
                                // x() converts at the use, so no load site waits for it before issuing the row loads
   int nr;
   // lane j: slot of row r0 + j of the frame (the frame's column of the sample-major slot map, stride NT)
+  // per_frame: the lane's offset is worked out again in every frame (three instructions) instead of kept across the frame
+  // loop in a register pair, which hg_stream_kernel at four wavefronts per SIMD does not have
   template <typename FC>
-  static __device__ __forceinline__ int load_slots(const FC& fc, const int32_t* scol, int r0, int R) {
+  static __device__ __forceinline__ int load_slots(const FC& fc, const int32_t* scol, int r0, int R, bool per_frame = false) {
     const int nr_ = R - r0 < RB ? R - r0 : RB;
+    int lane = fc.lane;
+    if (per_frame) asm volatile("" : "+v"(lane));
     // (a 32-bit BYTE offset from a uniform base: SGPR pair + one VGPR, no 64-bit address pair kept -- and spilled -- per lane)
-    return *reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(scol) + (unsigned)(r0 + (fc.lane < nr_ ? fc.lane : 0)) * (unsigned)fc.a.NT * 4u);
+    return *reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(scol) + (unsigned)(r0 + (lane < nr_ ? lane : 0)) * (unsigned)fc.a.NT * 4u);
   }
   // rows r0 .. r0+nr-1 of frame n, slots from load_slots
   template <typename FC>
@@ -574,6 +628,11 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1 && sizeof(ST) == 2) ? ST_
   // float rows (bf16x3 mode), one chunk: 32 rows x 4 registers at two wavefronts per SIMD hold the whole frame as well (16 per
   // batch re-read both batches in every pass: 3x the traffic of a kernel that is memory-bound with float rows)
   using RBt = RowBatch<NCH, ST, 1, RT, ((sizeof(ST) == 2 && NCH == 2 && KP <= 16) || (sizeof(ST) == 4 && NCH == 1 && KP <= 8)) ? 32 : 0>;
+  // The frame's wavefront sums grouped (common.h: sum_rows4_x2 / _x4), the rank sums of the H update four ranks at a time.
+  // Rank <= 8 only: at rank 16 and 32 every instantiation gains scratch with it (one chunk of bf16 rows, rank 32: 0 -> 140
+  // bytes; three chunks: 280 -> 1012), so those keep one chain per sum.
+  // One chunk of bf16 rows with 10 samples or any count (no TAIL) gains scratch as well (0 -> 12, 12 -> 28 bytes) and stays.
+  constexpr bool GRP = KP <= 8 && !(NCH == 1 && sizeof(ST) == 2 && RT != 30 && !TAIL);
   int n_beg, n_end;
   wave_frames(a.NT, n_beg, n_end);
   const bool one = a.R <= RBt::RB;                    // the frame fits one batch: its rows are read once
@@ -586,7 +645,7 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1 && sizeof(ST) == 2) ? ST_
     // (Requesting the operands a frame ahead, so that the rows go out at once, was measured: 0.179 against 0.172 ms.)
     const int utt = a.frame_utt[n];
     const float gn = a.g[n];
-    const int sl = RBt::load_slots(fc, srow, 0, a.R);
+    const int sl = RBt::load_slots(fc, srow, 0, a.R, GRP && NCH == 1 && sizeof(ST) == 2);
     f32x4 vb[NCH], x2[NCH];
     float vbx, x2x;
     fc.load_x2(n, x2, x2x);
@@ -625,8 +684,15 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1 && sizeof(ST) == 2) ? ST_
         };
         rb.for_rows(row1);
         const float q = fast_rcp(gn * rb.x() + vbx) * rb.xmask(fc);
-        a1x += wave_sum(q);
-        a2x += wave_sum(q * q);
+        if constexpr (GRP) {
+          float s1, s2;
+          wave_sum_pair(q, q * q, s1, s2);
+          a1x += s1;
+          a2x += s2;
+        } else {
+          a1x += wave_sum(q);
+          a2x += wave_sum(q * q);
+        }
       }
 #pragma unroll
       for (int c = 0; c < NCH; ++c)
@@ -639,13 +705,32 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1 && sizeof(ST) == 2) ? ST_
       a2x = lead ? a2x * x2x : 0.f;
       a1x = lead ? a1x : 0.f;
       float hn[KP];
+      if constexpr (GRP) {
+        // four ranks at a time: the lanes' partial sums of the group first, their eight in-row chains side by side, then one
+        // shared cross-row stage for the numerators and one for the denominators, which leave rank k0 + j in row j of both
 #pragma unroll
-      for (int k = 0; k < KP; ++k) {
-        float nu, de;
-        fc.w_dot(utt, k, a2, a1, a2x, a1x, nu, de);
-        nu = wave_sum(nu);
-        de = wave_sum(de);
-        hn[k] = vn_uniform(k < a.K ? hs[k] * __builtin_amdgcn_sqrtf(nu * fast_rcp(de)) : 0.f);       // mcem.py:121
+        for (int k0 = 0; k0 < KP; k0 += 4) {
+          float nu[4], de[4];
+          fc.w_dot4(utt, k0, a2, a1, a2x, a1x, nu, de);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) { nu[j] = sum_row16(nu[j]); de[j] = sum_row16(de[j]); }
+          const float nu4 = sum_rows4_x4(nu[0], nu[1], nu[2], nu[3]), de4 = sum_rows4_x4(de[0], de[1], de[2], de[3]);
+          const float rt = __builtin_amdgcn_sqrtf(nu4 * fast_rcp(de4));
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const float hv = hs[k0 + j] * rt, hj = read_lane(hv, 16 * j);
+            hn[k0 + j] = k0 + j < a.K ? hj : 0.f;                                                     // mcem.py:121
+          }
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < KP; ++k) {
+          float nu, de;
+          fc.w_dot(utt, k, a2, a1, a2x, a1x, nu, de);
+          nu = wave_sum(nu);
+          de = wave_sum(de);
+          hn[k] = vn_uniform(k < a.K ? hs[k] * __builtin_amdgcn_sqrtf(nu * fast_rcp(de)) : 0.f);     // mcem.py:121
+        }
       }
       if (fc.lane == 0) {
 #pragma unroll
@@ -677,8 +762,15 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1 && sizeof(ST) == 2) ? ST_
         };
         rb.for_rows(row2);
         const float q = fast_rcp(gn * rb.x() + vbx), vq = rb.x() * q * rb.xmask(fc);
-        dgx += wave_sum(vq);
-        ngx += wave_sum(vq * q);
+        if constexpr (GRP) {
+          float s1, s2;
+          wave_sum_pair(vq, vq * q, s1, s2);
+          dgx += s1;
+          ngx += s2;
+        } else {
+          dgx += wave_sum(vq);
+          ngx += wave_sum(vq * q);
+        }
       }
 #pragma unroll
       for (int c = 0; c < NCH; ++c)
@@ -688,8 +780,12 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1 && sizeof(ST) == 2) ? ST_
             if (!TAIL || fc.ok(c, t)) { nu += x2[c][t] * ng[c][t]; de += dg[c][t]; }
         }
       if (fc.lane == 0 && fc.has_x) { nu += x2x * ngx; de += dgx; }
-      nu = wave_sum(nu);
-      de = wave_sum(de);
+      if constexpr (GRP) {
+        wave_sum_pair(nu, de, nu, de);
+      } else {
+        nu = wave_sum(nu);
+        de = wave_sum(de);
+      }
     }
     const float gnew = gn * __builtin_amdgcn_sqrtf(nu * fast_rcp(de));                     // mcem.py:142
     if (fc.lane == 0) a.g[n] = gnew;
@@ -729,8 +825,15 @@ __global__ __launch_bounds__(256, (KP <= 8 && NCH == 1 && sizeof(ST) == 2) ? ST_
         }
       }
       const float xm = rb.xmask(fc), x0 = gnew * rb.x() + vbx;
-      clx += wave_sum(fast_log2(x0) * xm);
-      cxx += wave_sum(fast_rcp(x0) * xm);
+      if constexpr (GRP) {
+        float s1, s2;
+        wave_sum_pair(fast_log2(x0) * xm, fast_rcp(x0) * xm, s1, s2);
+        clx += s1;
+        cxx += s2;
+      } else {
+        clx += wave_sum(fast_log2(x0) * xm);
+        cxx += wave_sum(fast_rcp(x0) * xm);
+      }
     }
     float cs = 0.f;
 #pragma unroll

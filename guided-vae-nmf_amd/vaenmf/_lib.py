@@ -121,6 +121,7 @@ SIGNATURES = {
     "vaenmf_wchain_addressable": (_I, [_I64, _I, _I, _I, _I, _I, _I]),
     "vaenmf_store_layout": (_I, [_I, _I, _I, _I, _I64, _I, _P]),
     "vaenmf_hbm_read_probe": (_I, [_P, _I64, _I, _P, C.POINTER(_D), _P]),
+    "vaenmf_wave_sum_probe": (_I, [_P, _I, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -697,6 +697,13 @@ int vaenmf_profile_read(vaenmf_plan* p, double* ms, int64_t* counts);
  * `reps` timed sweeps after one untimed one; sink DEV (4 bytes, never written in practice).  Synchronises the stream. */
 int vaenmf_hbm_read_probe(const void* buf, int64_t bytes, int32_t reps, void* sink, double* gbps_out, void* stream);
 
+/* Test aid (no reference counterpart; not on the hot path): the wavefront sums the streaming kernels are built on, run on
+ * n sets of 4 x 64 floats, x DEV [n][4][64].  Every lane writes what it holds afterwards: one DEV [n][4][64], each of the
+ * four values summed on its own; x4 DEV [n][64], the four through one shared cross-row stage (lanes 16 j .. 16 j + 15 hold
+ * total j); x2 DEV [n][2][64], the pairs (0, 1) and (2, 3) (lanes 0-15 and 32-47 hold the pair's first total, lanes 16-31
+ * and 48-63 its second). */
+int vaenmf_wave_sum_probe(const float* x, int32_t n, float* one, float* x4, float* x2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
