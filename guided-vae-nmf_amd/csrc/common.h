@@ -97,7 +97,7 @@ struct vaenmf_plan {
   int Fs, Kp, NT3;           // padded bins, padded rank, feature tiles of 16 on the MFMA path of the last layer
   int Fm;                    // bins on the MFMA path: F-1 when F = 16k+1 (the odd last bin is computed in fp32 FMA), else F
   float* w3n;                // [HID] fp32 row F-1 of the last layer (odd last bin)
-  int geom;                  // workgroup geometry (engine.hip: launch_decode)
+  int geom;                  // workgroup geometry (engine.hip: with_geom)
   int nwaves;                // waves of a team that split the features
   int tile_frames;           // MH-chain frames per workgroup: 64 (2 teams of 4 waves) or 32 (1 team of 8)
   // decoder weights on the device, MFMA fragment order (see weights in plan.hip)
@@ -203,7 +203,7 @@ VnStoreLayout vn_store_layout(const vaenmf_plan* p, int Rs, bool m2);           
 int vn_launch_wchain(vaenmf_plan* p, const VnChainCall& cc, hipStream_t st);      // chain.hip: builds WcArgs, picks the kernel
 int vn_launch_tchain(vaenmf_plan* p, const VnChainCall& cc, hipStream_t st);      // engine.hip: builds ChainArgs, picks the geometry
 int vn_launch_widechain(vaenmf_plan* p, const VnChainCall& cc, hipStream_t st);   // wide.hip: the chain of a wide plan
-int vn_launch_wide_rng_fill(vaenmf_plan* p, uint32_t call, int S, float* eps_out, float* u_out, hipStream_t st);   // wide.hip
+int vn_launch_wide_rng_fill(vaenmf_plan* p, uint32_t call, int S, float* eps_out, float* u_out, hipStream_t st);   // engine.hip: rng_fill_kernel over the wave tiles
 int vn_launch_w_update(const vaenmf_plan* p, float* W, const float* Ht, hipStream_t st);                // aux.hip
 int vn_launch_w_update_tiles(const vaenmf_plan* p, float* W, hipStream_t st, bool groups);             // aux.hip
 int vn_launch_cost_reduce(const vaenmf_plan* p, const double* cost_frames, size_t stride, int n_it, int R, double* cost, int niter,
@@ -252,6 +252,83 @@ __device__ __forceinline__ void split4(const f32x4 v, bf16x4& hi, bf16x4& lo) {
     hi[t] = h;
     lo[t] = (__bf16)(v[t] - (float)h);
   }
+}
+
+// 8 floats -> the bf16 (hi, lo) parts of one MFMA operand (lo is zero in bf16 mode)
+template <bool SPLIT>
+__device__ __forceinline__ void split8(const float (&z)[8], bf16x8& hi, bf16x8& lo) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    __bf16 h = (__bf16)z[j];
+    hi[j] = h;
+    lo[j] = SPLIT ? (__bf16)(z[j] - (float)h) : (__bf16)0.f;
+  }
+}
+
+// ---- fragment blocks [part hi/lo][lane][8 bf16] of the team and wide kernels (engine.hip's header has the order) ----
+// this lane's MFMA operand of the block at p (p includes lane16 = 16 * lane): the lo part sits 1024 bytes behind the hi
+// part in bf16x3 mode; bf16 mode has none (and mma3 reads none)
+template <bool SPLIT>
+__device__ __forceinline__ void load_frag(const char* p, bf16x8& hi, bf16x8& lo) {
+  hi = *reinterpret_cast<const bf16x8*>(p);
+  if (SPLIT) lo = *reinterpret_cast<const bf16x8*>(p + 1024); else lo = hi;
+}
+// tanh, split and store feature tile t of a layer into the activation image [k-step][part][lane][8 bf16] of one column
+// group: tile t is half (t & 1) of k-step t >> 1.  Returns the tanh values.
+template <bool SPLIT>
+__device__ __forceinline__ f32x4 store_act_tile(char* img, unsigned lane16, int t, const f32x4 acc) {
+  f32x4 h;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) h[k] = fast_tanh(acc[k]);
+  bf16x4 hi, lo;
+  split4(h, hi, lo);
+  char* p = img + (t >> 1) * (SPLIT ? 2 : 1) * 1024 + lane16 + (t & 1) * 8;
+  *reinterpret_cast<bf16x4*>(p) = hi;
+  if (SPLIT) *reinterpret_cast<bf16x4*>(p + 1024) = lo;
+  return h;
+}
+
+// a latent row in fragment order: eight floats <-> the quads at row + o0 and row + o1 (team kernels: latents 4q.. and
+// 16 + 4q..; wide kernel: the same inside k-step w)
+__device__ __forceinline__ void load_row8(const float* row, int o0, int o1, float (&z)[8]) {
+  const f32x4 lo = *reinterpret_cast<const f32x4*>(row + o0);
+  const f32x4 hi = *reinterpret_cast<const f32x4*>(row + o1);
+#pragma unroll
+  for (int t = 0; t < 4; ++t) { z[t] = lo[t]; z[4 + t] = hi[t]; }
+}
+__device__ __forceinline__ void store_row8(float* row, int o0, int o1, const float (&z)[8]) {
+  *reinterpret_cast<f32x4*>(row + o0) = f32x4{z[0], z[1], z[2], z[3]};
+  *reinterpret_cast<f32x4*>(row + o1) = f32x4{z[4], z[5], z[6], z[7]};
+}
+
+// (widechain_kernel; mh_chain_kernel keeps the same lines written out)
+// Per-(bin, frame) constants of a chain in accumulator layout, for the bins f0 .. f0 + 3 of one frame: X2, and Vb = W H
+// (mcem.py:81-82) or the plan's fixed Vb [NT][Fs] (non-null).  X2 [NT][Fs], W [utt][Fs][Kp], Ht [NT][Kp]; n: the frame's row, utt: its utterance.  A tile the
+// wavefront does not own (!own) and the padding bins (>= F_end) get X2 = 0, Vb = 1; with Vs = 0 there (zero W3 rows, a
+// large negative bias) their energy term is exactly 0.
+__device__ __forceinline__ void tile_consts4(bool own, const float* X2, const float* Vb, const float* W, const float* Ht, int Fs, int Kp,
+                                             int n, int utt, int f0, int F_end, f32x4& x2, f32x4& vb) {
+  f32x4 xv = {0, 0, 0, 0}, v = {0, 0, 0, 0};
+  if (own) {
+    xv = *reinterpret_cast<const f32x4*>(X2 + (size_t)n * Fs + f0);
+    if (Vb) {
+      v = *reinterpret_cast<const f32x4*>(Vb + (size_t)n * Fs + f0);
+    } else {
+      for (int k = 0; k < Kp; k += 4) {
+        const f32x4 h = *reinterpret_cast<const f32x4*>(Ht + (size_t)n * Kp + k);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const f32x4 wr = *reinterpret_cast<const f32x4*>(W + ((size_t)utt * Fs + f0 + t) * Kp + k);
+          v[t] += wr[0] * h[0] + wr[1] * h[1] + wr[2] * h[2] + wr[3] * h[3];
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+    if (f0 + t >= F_end) { xv[t] = 0.f; v[t] = 1.f; }
+  x2 = xv;
+  vb = v;
 }
 
 // one MFMA step of a decoder layer: bf16x3 (SPLIT) adds the two cross terms of the (hi, lo) parts

@@ -1,6 +1,6 @@
 // MH-chain and sample-decode kernels: the hot loop of the VAE-NMF reconstruct path.
 //
-// Both kernels evaluate the decoder MLP (python/models/models.py:118-121) on MFMA
+// mh_chain_kernel and decode_kernel evaluate the decoder MLP (python/models/models.py:118-121) on MFMA
 // (v_mfma_f32_16x16x32_bf16, fp32 accumulate).  The MLP input rows are the MFMA
 // *column* dimension (16 per column group), the features are MFMA rows split over
 // the waves of a workgroup, so an accumulator tile of one layer is, after tanh and a
@@ -15,6 +15,11 @@
 //
 // PREC: bf16x3 computes w_hi*a_hi + w_lo*a_hi + w_hi*a_lo (error ~2^-17 per product);
 //       bf16 computes w_hi*a_hi only.
+//
+// What these kernels share with the wide chain (wide.hip) is in common.h: split8, the fragment loader load_frag, the load of
+// a latent row.  wide.hip takes more from there (the tanh-split-store of a tile, the row stores, the per-tile constants
+// X2 and Vb = W H); here those stay written out, because every form of sharing them changed the instructions of these
+// kernels.
 #include "common.h"
 
 namespace {
@@ -83,16 +88,6 @@ __device__ __forceinline__ f32x4 mma3_flip(const bf16x8 ahi, const bf16x8 alo, c
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(ahi, whi, acc, 0, 0, 0);
 }
 
-template <bool SPLIT>
-__device__ __forceinline__ void split8(const float (&z)[8], bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    __bf16 h = (__bf16)z[j];
-    hi[j] = h;
-    lo[j] = SPLIT ? (__bf16)(z[j] - (float)h) : (__bf16)0.f;
-  }
-}
-
 // Everything a wave needs to run the decoder: LDS pointers + its (uniform) team / wave index.
 template <int NW, int NTEAM, int MT, bool SPLIT, bool W3LDS>
 struct Dec {
@@ -120,26 +115,16 @@ struct Dec {
 
   static __device__ __forceinline__ int act_off(int cg, int s) { return (cg * NK_H + s) * M::PARTS * 1024; }
 
+  // the fragment loaders: the address arithmetic of each block, then load_frag (common.h)
   __device__ __forceinline__ void lds_w(int base, int tile, int nk, int s, bf16x8& hi, bf16x8& lo) const {
-    const char* p = lds + base + ((tile * nk + s) * M::PARTS) * 1024 + lane16;
-    hi = *reinterpret_cast<const bf16x8*>(p);
-    if (SPLIT) lo = *reinterpret_cast<const bf16x8*>(p + 1024); else lo = hi;
+    load_frag<SPLIT>(lds + base + ((tile * nk + s) * M::PARTS) * 1024 + lane16, hi, lo);
   }
   __device__ __forceinline__ void w3_frag(int i, int s, bf16x8& hi, bf16x8& lo) const {
-    if (W3LDS) {
-      const char* p = w3l + (((w + NW * i) * NK_H + s) * M::PARTS) * 1024 + lane16;
-      hi = *reinterpret_cast<const bf16x8*>(p);
-      if (SPLIT) lo = *reinterpret_cast<const bf16x8*>(p + 1024); else lo = hi;
-    } else {
-      const char* p = w3g + (size_t)((i * NW * NK_H + s) * 2) * 1024 + lane16;
-      hi = *reinterpret_cast<const bf16x8*>(p);
-      if (SPLIT) lo = *reinterpret_cast<const bf16x8*>(p + 1024); else lo = hi;
-    }
+    if (W3LDS) load_frag<SPLIT>(w3l + (((w + NW * i) * NK_H + s) * M::PARTS) * 1024 + lane16, hi, lo);
+    else load_frag<SPLIT>(w3g + (size_t)((i * NW * NK_H + s) * 2) * 1024 + lane16, hi, lo);
   }
   __device__ __forceinline__ void act_frag(const char* img, int cg, int s, bf16x8& hi, bf16x8& lo) const {
-    const char* p = img + act_off(cg, s) + lane16;
-    hi = *reinterpret_cast<const bf16x8*>(p);
-    if (SPLIT) lo = *reinterpret_cast<const bf16x8*>(p + 1024); else lo = hi;
+    load_frag<SPLIT>(img + act_off(cg, s) + lane16, hi, lo);
   }
   // split + store one tile of activations (feature tile `tile`, already tanh'ed) into an LDS image
   __device__ __forceinline__ void store_h(char* img, int cg, int tile, const f32x4 h) const {
@@ -249,11 +234,12 @@ struct Dec {
     team_sync();
   }
 
-  // Last layer, tile-major: the activation fragments of all k-steps are read once, then each bin tile is
-  // finished (MFMAs over the k-steps) and handed to `epi(i, acc0, acc1)` before the next one starts, so the
-  // VALU epilogue of tile i can run under the MFMAs of tile i+1 (same wave, independent instructions).
-  template <bool FLIP, typename BIAS, typename EPI>
-  __device__ __forceinline__ void out_layer_tiles(BIAS bias, EPI epi) const {
+  // Output layer of the chain, bins x frames (acc rows = bins 16 tile + 4q + t, columns = the frames of a column group),
+  // tile-major: the activation fragments of all k-steps are read once, then each bin tile is finished (MFMAs over the
+  // k-steps) and handed to `epi(i, acc0, acc1)` before the next one starts, so the VALU epilogue of tile i can run under
+  // the MFMAs of tile i+1 (same wave, independent instructions).
+  template <typename BIAS, typename EPI>
+  __device__ __forceinline__ void out_bins_by_frames(BIAS bias, EPI epi) const {
     bf16x8 ahi[NK_H][2], alo[NK_H][2];
 #pragma unroll
     for (int s = 0; s < NK_H; ++s) {
@@ -271,19 +257,16 @@ struct Dec {
           bf16x8 whi, wlo;
           w3_frag(i, s, whi, wlo);
 #pragma unroll
-          for (int cg = 0; cg < 2; ++cg)
-            acc[cg] = FLIP ? mma3_flip<SPLIT>(ahi[s][cg], alo[s][cg], whi, wlo, acc[cg])
-                           : mma3<SPLIT>(whi, wlo, ahi[s][cg], alo[s][cg], acc[cg]);
+          for (int cg = 0; cg < 2; ++cg) acc[cg] = mma3<SPLIT>(whi, wlo, ahi[s][cg], alo[s][cg], acc[cg]);
         }
         epi(i, acc[0], acc[1]);
       }
     }
   }
 
-  // Last layer.  FLIP=false: acc[i][cg] rows = bins 16*tile+4q+t, cols = columns (frames);
-  //              FLIP=true : acc[i][cg] rows = columns (samples) 4q+t, col = bin 16*tile+c.
-  template <bool FLIP>
-  __device__ __forceinline__ void out_layer(f32x4 (&acc)[MT][2]) const {
+  // Output layer of decoding, samples x bins (acc[i][cg] rows = the samples 4q + t of a column group, column = bin
+  // 16 tile + c), k-step-major: the activations are the A operand here (mma3_flip).
+  __device__ __forceinline__ void out_samples_by_bins(f32x4 (&acc)[MT][2]) const {
 #pragma unroll
     for (int s = 0; s < NK_H; ++s) {
       bf16x8 ahi[2], alo[2];
@@ -295,16 +278,14 @@ struct Dec {
           bf16x8 whi, wlo;
           w3_frag(i, s, whi, wlo);
 #pragma unroll
-          for (int cg = 0; cg < 2; ++cg)
-            acc[i][cg] = FLIP ? mma3_flip<SPLIT>(ahi[cg], alo[cg], whi, wlo, acc[i][cg])
-                              : mma3<SPLIT>(whi, wlo, ahi[cg], alo[cg], acc[i][cg]);
+          for (int cg = 0; cg < 2; ++cg) acc[i][cg] = mma3_flip<SPLIT>(ahi[cg], alo[cg], whi, wlo, acc[i][cg]);
         }
       }
     }
   }
 };
 
-// workgroup prologue shared by both kernels: stage W1/W2 (and W3 when it fits), b2, b3 into LDS
+// workgroup prologue of mh_chain_kernel and decode_kernel: stage W1/W2 (and W3 when it fits), b2, b3 into LDS
 template <int NW, int NTEAM, int MT, bool SPLIT, bool W3LDS>
 __device__ __forceinline__ Dec<NW, NTEAM, MT, SPLIT, W3LDS> dec_setup(char* smem, const DecW& dw, int w3_lds_off, int Fs) {
   using M = LdsMap<NTEAM, SPLIT>;
@@ -466,12 +447,7 @@ __global__ __launch_bounds__(NW * NTEAM * 64) void mh_chain_kernel(const ChainAr
   // ---- current latent state, fragment order: latents 4q..4q+3 and 16+4q..16+4q+3
   float z[2][8];
 #pragma unroll
-  for (int fg = 0; fg < 2; ++fg) {
-    const f32x4 lo = *reinterpret_cast<const f32x4*>(a.Z + (size_t)nrow[fg] * LAT + 4 * q);
-    const f32x4 hi = *reinterpret_cast<const f32x4*>(a.Z + (size_t)nrow[fg] * LAT + 16 + 4 * q);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) { z[fg][t] = lo[t]; z[fg][4 + t] = hi[t]; }
-  }
+  for (int fg = 0; fg < 2; ++fg) load_row8(a.Z + (size_t)nrow[fg] * LAT, 4 * q, 16 + 4 * q, z[fg]);
   // ---- sample-variance store (STORE): the decoded variances Vs = exp(decoder(Z')) of every post-burn-in
   // proposal go to HBM (slot r of the frame for step burnin + r) so that the M-step streams them instead of
   // decoding the samples again; slot R holds the state the chain is in when the burn-in ends (one extra
@@ -537,7 +513,7 @@ __global__ __launch_bounds__(NW * NTEAM * 64) void mh_chain_kernel(const ChainAr
     split8<SPLIT>(zz[1], zhi[1], zlo[1]);
     d.hidden(zhi, zlo, bias1, [&]() { if (next_step < S) draw(next_step); });
     double e[2] = {0.0, 0.0};
-    d.template out_layer_tiles<false>(
+    d.out_bins_by_frames(
         [&](int i) { return *reinterpret_cast<const f32x4*>(b3l + 16 * (w + NW * i) + 4 * q); },
         [&](int i, const f32x4 acc0, const f32x4 acc1) {
 #pragma unroll
@@ -696,18 +672,21 @@ __global__ __launch_bounds__(NW * NTEAM * 64) void mh_chain_kernel(const ChainAr
   }
 }
 
-// same streams as mh_chain_kernel::draw, written to global memory (test aid); blockDim = 8 * tile frames
+// The chain kernels' noise streams written to global memory (test aid): thread <-> (frame of the tile, latent quad) with
+// qpf quads per frame and rows of `width` floats -- 8 and LAT for mh_chain_kernel::draw over the team tiles, 32 and 128
+// for widechain_kernel (wide.hip) over the wave tiles; blockDim = qpf * frames of a tile.  (A run-time divide where the two
+// kernels had shifts: a test aid, not a hot path.)
 __global__ void rng_fill_kernel(const int32_t* tile_utt, const int32_t* tile_n0, const int32_t* tile_cnt,
                                 const int32_t* frame_off, const uint64_t* utt_seed, uint32_t call, int S, int NT,
-                                float* eps_out, float* u_out) {
-  const int tile = blockIdx.x, sid = threadIdx.x, sfr = sid >> 3, squad = sid & 7;
+                                int qpf, int width, float* eps_out, float* u_out) {
+  const int tile = blockIdx.x, sid = threadIdx.x, sfr = sid / qpf, squad = sid - sfr * qpf;
   const int utt = tile_utt[tile], n0 = tile_n0[tile], cnt = tile_cnt[tile];
   if (sfr >= cnt) return;
   Xs128 st = xs_seed(utt_seed[utt], (uint32_t)(n0 - frame_off[utt] + sfr), (uint32_t)squad, call);
   for (int s = 0; s < S; ++s) {
     const f32x4 e = normal4(st);
     const size_t row = (size_t)s * NT + n0 + sfr;
-    *reinterpret_cast<f32x4*>(eps_out + row * LAT + 4 * squad) = e;
+    *reinterpret_cast<f32x4*>(eps_out + row * width + 4 * squad) = e;
     if (squad == 0) u_out[row] = uniform01(st);
   }
 }
@@ -783,6 +762,7 @@ __global__ __launch_bounds__(NW * NTEAM * 64) void decode_kernel(const DecodeArg
 #pragma unroll
   for (int ti = 0; ti < TPW; ++ti) bias1_m1[ti] = *reinterpret_cast<const f32x4*>(dw.b1 + 16 * (w + NW * ti) + 4 * q);
 
+  // ==== frame driver (every mode): tile loop, W staging, input prefetch, per-bin constants, decode_tiles / decode_chunk ====
   // one tile (frames of one utterance) at a time; the teams take alternate frames of the tile
   for (int tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
   const int utt = a.tile_utt[tile];
@@ -950,7 +930,7 @@ __global__ __launch_bounds__(NW * NTEAM * 64) void decode_kernel(const DecodeArg
           mkn[sg] = (32 * ch + 16 * sg + c < a.R) ? 1.f : 0.f;
         }
       }
-      // (the k-step-major form measured faster here than Dec::out_layer_tiles: wstats 0.303 vs 0.312 ms)
+      // (the k-step-major form measured faster here than Dec::out_bins_by_frames' tile-major one: wstats 0.303 vs 0.312 ms)
       f32x4 va[MAXT][2];
 #pragma unroll
       for (int i = 0; i < MAXT; ++i) {
@@ -958,7 +938,7 @@ __global__ __launch_bounds__(NW * NTEAM * 64) void decode_kernel(const DecodeArg
         va[i][0] = f32x4{bv, bv, bv, bv};
         va[i][1] = va[i][0];
       }
-      d.template out_layer<true>(va);
+      d.out_samples_by_bins(va);
 #pragma unroll
       for (int i = 0; i < MAXT; ++i)
         if (d.tile_ok(i)) {
@@ -976,6 +956,10 @@ __global__ __launch_bounds__(NW * NTEAM * 64) void decode_kernel(const DecodeArg
     auto sum_q = [&](float v) { return sum_rows4(v); };
     auto sum_c = [&](float v) { return sum_row16(v); };
 
+    // ==== the modes.  Tile values are vs[i][sg][t] with vb[i] and the sample mask, summed over q; the odd last bin is
+    // column-on-lane -- vsn[sg] with vbn and mkn[sg], summed over c -- and follows each tile pass as its scalar twin.
+    // (The twins stay written out: shared through lambdas they changed registers and speed) ====
+    // ---- MODE_STORE (compute_Vs, mcem.py:444-454): the variances themselves, zeros in the padding bins
     if (MODE == MODE_STORE) {
       for (int ch = 0; ch < nch; ++ch) {
         f32x4 vs[MAXT][2];
@@ -1003,6 +987,7 @@ __global__ __launch_bounds__(NW * NTEAM * 64) void decode_kernel(const DecodeArg
       continue;
     }
 
+    // ---- MODE_WSTATS
     if (MODE == MODE_WSTATS) {
       // A1 = sum_r 1/Vx, A2 = sum_r 1/Vx^2 with the pre-update variances (mcem.py:107-109)
       float a1[MAXT], a2[MAXT], a1n = 0.f, a2n = 0.f;
@@ -1042,6 +1027,7 @@ __global__ __launch_bounds__(NW * NTEAM * 64) void decode_kernel(const DecodeArg
           a.P[(size_t)n * a.Fs + dw.F - 1 + c] = c == 0 ? x2n * s2 : 0.f;
         }
       }
+    // ---- MODE_WF
     } else if (MODE == MODE_WF) {
       // WFs = mean_r(g Vs / Vx), WFn = mean_r(Vb / Vx)  (mcem.py:486-488)
       float ws[MAXT], wn[MAXT], wsn = 0.f, wnn = 0.f;
@@ -1095,6 +1081,7 @@ __global__ __launch_bounds__(NW * NTEAM * 64) void decode_kernel(const DecodeArg
           if (a.WFn) a.WFn[o] = fval[i] ? nn : 0.f;
         }
       }
+    // ---- MODE_HG: H, variances with the new H, g, cost; MODE_G (fixed noise model): g and cost only
     } else if (MODE == MODE_HG || MODE == MODE_G) {
       f32x4 vs[MAXT][2];
       // chunk validity mask (chunk 0 uses mk; later chunks are rare: R > 32)
@@ -1329,68 +1316,56 @@ void lds_plan(int NT3, size_t extra_per_team, int* w3_off, size_t* total) {
   else { *w3_off = -1; *total = base; }
 }
 
-template <int NW, int NTEAM, int MT, bool SPLIT, bool STORE>
-int launch_chain_s(ChainArgs a, int n_tiles, hipStream_t st) {
-  size_t lds;
-  lds_plan<NTEAM, SPLIT>(a.dw.NT3, sizeof(ChainX), &a.w3_lds_off, &lds);
-  const dim3 blk(NW * NTEAM * 64);
-  if (a.w3_lds_off >= 0) {
-    if (int e = vn_ensure_dyn_lds((const void*)mh_chain_kernel<NW, NTEAM, MT, SPLIT, true, STORE>, VN_LDS_LIMIT)) return e;
-    hipLaunchKernelGGL((mh_chain_kernel<NW, NTEAM, MT, SPLIT, true, STORE>), dim3(n_tiles), blk, lds, st, a);
-  } else {
-    if (int e = vn_ensure_dyn_lds((const void*)mh_chain_kernel<NW, NTEAM, MT, SPLIT, false, STORE>, VN_LDS_LIMIT)) return e;
-    hipLaunchKernelGGL((mh_chain_kernel<NW, NTEAM, MT, SPLIT, false, STORE>), dim3(n_tiles), blk, lds, st, a);
+template <int V> using ic = std::integral_constant<int, V>;
+// The one switch over the workgroup geometry and the precision: fn(ic<NW>, ic<NTEAM>, ic<MT>, bool_constant<SPLIT>).
+// plan.hip picks the geometry from the number of bin tiles NT3 of the MFMA path:
+//   0 = 2 teams x 4 waves, 5 bin tiles per wave (NT3 <= 20)      3 = 2 teams x 4 waves, 4 tiles (NT3 == 16)
+//   2 = 1 team  x 8 waves, 5 bin tiles per wave (NT3 <= 40)      4 = 1 team  x 8 waves, 4 tiles (NT3 == 32)
+template <typename FN>
+int with_geom(const vaenmf_plan* p, FN fn) {
+  auto prec = [&](auto nw, auto nteam, auto mt) {
+    return p->cfg.precision == VAENMF_PREC_BF16X3 ? fn(nw, nteam, mt, std::true_type{}) : fn(nw, nteam, mt, std::false_type{});
+  };
+  switch (p->geom) {
+    case 0: return prec(ic<4>{}, ic<2>{}, ic<5>{});
+    case 3: return prec(ic<4>{}, ic<2>{}, ic<4>{});
+    case 4: return prec(ic<8>{}, ic<1>{}, ic<4>{});
+    default: return prec(ic<8>{}, ic<1>{}, ic<5>{});
   }
-  return 0;
 }
-template <int NW, int NTEAM, int MT, bool SPLIT>
-int launch_chain(const ChainArgs& a, int n_tiles, hipStream_t st) {
-  return a.VsS ? launch_chain_s<NW, NTEAM, MT, SPLIT, true>(a, n_tiles, st) : launch_chain_s<NW, NTEAM, MT, SPLIT, false>(a, n_tiles, st);
+// ensure the dynamic LDS, then launch the W3LDS instantiation that a.w3_lds_off selects; kern(bool_constant<W3LDS>) names it
+template <typename KERN, typename ARGS>
+int launch_w3(KERN kern, const ARGS& a, int grid, int threads, size_t lds, hipStream_t st) {
+  auto go = [&](auto* fn) -> int {
+    if (int e = vn_ensure_dyn_lds((const void*)fn, VN_LDS_LIMIT)) return e;
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(threads), lds, st, a);
+    return 0;
+  };
+  return a.w3_lds_off >= 0 ? go(kern(std::true_type{})) : go(kern(std::false_type{}));
 }
 
-template <int NW, int NTEAM, int MT, bool SPLIT, int MODE, int KP>
-int launch_decode_one(const DecodeArgs& a, int grid, size_t lds, hipStream_t st) {
-  const dim3 blk(NW * NTEAM * 64);
-  if (a.w3_lds_off >= 0) {
-    if (int e = vn_ensure_dyn_lds((const void*)decode_kernel<NW, NTEAM, MT, SPLIT, true, MODE, KP>, VN_LDS_LIMIT)) return e;
-    hipLaunchKernelGGL((decode_kernel<NW, NTEAM, MT, SPLIT, true, MODE, KP>), dim3(grid), blk, lds, st, a);
-  } else {
-    if (int e = vn_ensure_dyn_lds((const void*)decode_kernel<NW, NTEAM, MT, SPLIT, false, MODE, KP>, VN_LDS_LIMIT)) return e;
-    hipLaunchKernelGGL((decode_kernel<NW, NTEAM, MT, SPLIT, false, MODE, KP>), dim3(grid), blk, lds, st, a);
-  }
-  return 0;
-}
-template <int NW, int NTEAM, int MT, bool SPLIT, int MODE>
-int launch_decode_kp(DecodeArgs a, int Kp, int grid, hipStream_t st) {
-  size_t lds;
-  // per team: DecodeX; per workgroup: the staged W[utt] (rank <= 8), placed right after the DecodeX blocks
-  const size_t wl_bytes = (Kp == 8 && MODE != MODE_STORE && MODE != MODE_G) ? (size_t)a.Fs * 8 * sizeof(float) : 0;
-  const size_t x_bytes = (NTEAM * sizeof(DecodeX) + 15) / 16 * 16;
-  lds_plan<NTEAM, SPLIT>(a.dw.NT3, (x_bytes + wl_bytes + NTEAM - 1) / NTEAM, &a.w3_lds_off, &lds);
-  a.wl_lds_off = (int)(LdsMap<NTEAM, SPLIT>::common_end + x_bytes);
-  switch (Kp) {
-    case 8:  return launch_decode_one<NW, NTEAM, MT, SPLIT, MODE, 8>(a, grid, lds, st);
-    case 16: return launch_decode_one<NW, NTEAM, MT, SPLIT, MODE, 16>(a, grid, lds, st);
-    default: return launch_decode_one<NW, NTEAM, MT, SPLIT, MODE, 32>(a, grid, lds, st);
-  }
-}
-// workgroup geometry (plan.hip picks it from the number of bin tiles NT3 of the MFMA path):
-//   0 = 2 teams x 4 waves, 5 bin tiles per wave (NT3 <= 20)      3 = 2 teams x 4 waves, 4 tiles (NT3 <= 16)
-//   2 = 1 team  x 8 waves, 5 bin tiles per wave (NT3 <= 40)      4 = 1 team  x 8 waves, 4 tiles (NT3 <= 32)
 template <int MODE>
-int launch_decode(const vaenmf_plan* p, const DecodeArgs& a, hipStream_t st) {
+int launch_decode(const vaenmf_plan* p, DecodeArgs a, hipStream_t st) {
   const int want = p->n_sms * 2;
   int grid = a.n_tiles < want ? a.n_tiles : want;
   const int cap = vn_switches().grid_cap;               // (tests: a small grid makes every workgroup walk several tiles)
   if (cap > 0 && cap < grid) grid = cap;
-  const bool split = p->cfg.precision == VAENMF_PREC_BF16X3;
   const int Kp = (MODE == MODE_STORE) ? 8 : p->Kp;
-  switch (p->geom) {
-    case 0: return split ? launch_decode_kp<4, 2, 5, true, MODE>(a, Kp, grid, st) : launch_decode_kp<4, 2, 5, false, MODE>(a, Kp, grid, st);
-    case 3: return split ? launch_decode_kp<4, 2, 4, true, MODE>(a, Kp, grid, st) : launch_decode_kp<4, 2, 4, false, MODE>(a, Kp, grid, st);
-    case 4: return split ? launch_decode_kp<8, 1, 4, true, MODE>(a, Kp, grid, st) : launch_decode_kp<8, 1, 4, false, MODE>(a, Kp, grid, st);
-    default: return split ? launch_decode_kp<8, 1, 5, true, MODE>(a, Kp, grid, st) : launch_decode_kp<8, 1, 5, false, MODE>(a, Kp, grid, st);
-  }
+  return with_geom(p, [&](auto nw, auto nteam, auto mt, auto split) -> int {
+    constexpr int NW = decltype(nw)::value, NTEAM = decltype(nteam)::value, MT = decltype(mt)::value;
+    constexpr bool SPLIT = decltype(split)::value;
+    size_t lds;
+    // per team: DecodeX; per workgroup: the staged W[utt] (rank <= 8), placed right after the DecodeX blocks
+    const size_t wl_bytes = (Kp == 8 && MODE != MODE_STORE && MODE != MODE_G) ? (size_t)a.Fs * 8 * sizeof(float) : 0;
+    const size_t x_bytes = (NTEAM * sizeof(DecodeX) + 15) / 16 * 16;
+    lds_plan<NTEAM, SPLIT>(a.dw.NT3, (x_bytes + wl_bytes + NTEAM - 1) / NTEAM, &a.w3_lds_off, &lds);
+    a.wl_lds_off = (int)(LdsMap<NTEAM, SPLIT>::common_end + x_bytes);
+    auto rank = [&](auto kp) {
+      return launch_w3([](auto w3) { return &decode_kernel<NW, NTEAM, MT, SPLIT, decltype(w3)::value, MODE, decltype(kp)::value>; },
+                       a, grid, NW * NTEAM * 64, lds, st);
+    };
+    return Kp == 8 ? rank(ic<8>{}) : (Kp == 16 ? rank(ic<16>{}) : rank(ic<32>{}));
+  });
 }
 
 DecodeArgs base_decode_args(const vaenmf_plan* p, const float* Zs, int Rcap, int R, const float* B1) {
@@ -1399,6 +1374,13 @@ DecodeArgs base_decode_args(const vaenmf_plan* p, const float* Zs, int Rcap, int
   a.Zs = Zs; a.B1 = B1; a.tile_utt = p->d_tile_utt; a.tile_n0 = p->d_tile_n0; a.tile_cnt = p->d_tile_cnt; a.n_tiles = p->n_tiles;
   a.Fs = p->Fs; a.K = p->cfg.K; a.NT = p->NT; a.Rcap = Rcap; a.R = R; a.Vb = p->Vb_ext;
   return a;
+}
+
+// the step-wise decoding entry points have no wide form
+int require_narrow(const vaenmf_plan* p, const char* entry) {
+  VN_REQUIRE(!p->wide, "%s: a wide decoder plan (z_dim > 32 or a hidden layer of 256 units) has no decoding kernels; run the chain with the sample "
+             "store on (vaenmf_sample_store) and use vaenmf_m_step_stored / vaenmf_wiener_stored (vaenmf_sample_store_gather for the variances)", entry);
+  return 0;
 }
 
 }  // namespace
@@ -1414,33 +1396,46 @@ int vn_launch_tchain(vaenmf_plan* p, const VnChainCall& cc, hipStream_t st) {
   a.utt_seed = p->d_utt_seed; a.eps = cc.eps; a.u = cc.u;
   a.Fs = p->Fs; a.Kp = p->Kp; a.NT = p->NT; a.Rcap = cc.Rcap; a.nsamples = cc.nsamples; a.burnin = cc.burnin;
   a.rng_mode = cc.rng_mode; a.call = cc.call; a.sd = cc.sd; a.update_Z = cc.update_Z;
-  const bool split = p->cfg.precision == VAENMF_PREC_BF16X3;
-  int lrc = 0;
-  switch (p->geom) {
-    case 0: lrc = split ? launch_chain<4, 2, 5, true>(a, p->n_tiles, st) : launch_chain<4, 2, 5, false>(a, p->n_tiles, st); break;
-    case 3: lrc = split ? launch_chain<4, 2, 4, true>(a, p->n_tiles, st) : launch_chain<4, 2, 4, false>(a, p->n_tiles, st); break;
-    case 4: lrc = split ? launch_chain<8, 1, 4, true>(a, p->n_tiles, st) : launch_chain<8, 1, 4, false>(a, p->n_tiles, st); break;
-    default: lrc = split ? launch_chain<8, 1, 5, true>(a, p->n_tiles, st) : launch_chain<8, 1, 5, false>(a, p->n_tiles, st); break;
-  }
+  const int lrc = with_geom(p, [&](auto nw, auto nteam, auto mt, auto split) -> int {
+    constexpr int NW = decltype(nw)::value, NTEAM = decltype(nteam)::value, MT = decltype(mt)::value;
+    constexpr bool SPLIT = decltype(split)::value;
+    size_t lds;
+    lds_plan<NTEAM, SPLIT>(a.dw.NT3, sizeof(ChainX), &a.w3_lds_off, &lds);
+    auto store = [&](auto store_on) {
+      return launch_w3([](auto w3) { return &mh_chain_kernel<NW, NTEAM, MT, SPLIT, decltype(w3)::value, decltype(store_on)::value>; },
+                       a, p->n_tiles, NW * NTEAM * 64, lds, st);
+    };
+    return cc.VsS ? store(std::true_type{}) : store(std::false_type{});
+  });
   if (lrc) return lrc;
   VN_CHECK_HIP(hipGetLastError());
   p->last_chain_kernel = 0;
   return 0;
 }
 
-extern "C" int vaenmf_rng_fill(vaenmf_plan* p, uint32_t call, int32_t S, float* eps_out, float* u_out, void* stream) {
-  if (int e = check_bound(p)) return e;
-  if (p->wide) return vn_launch_wide_rng_fill(p, call, S, eps_out, u_out, (hipStream_t)stream);    // [S][NT][128], 32 quads per frame
-  hipLaunchKernelGGL(rng_fill_kernel, dim3(p->n_tiles), dim3(8 * p->tile_frames), 0, (hipStream_t)stream, p->d_tile_utt, p->d_tile_n0,
-                     p->d_tile_cnt, p->d_frame_off, p->d_utt_seed, call, S, p->NT, eps_out, u_out);
+// the one rng_fill_kernel over a plan's tile tables: `frames` frames per tile, Lp / 4 quads of a frame's Lp latents
+static int launch_rng_fill(vaenmf_plan* p, int n_tiles, int frames, const int32_t* t_utt, const int32_t* t_n0, const int32_t* t_cnt, uint32_t call,
+                           int S, float* eps_out, float* u_out, hipStream_t st) {
+  const int qpf = p->Lp / 4;
+  hipLaunchKernelGGL(rng_fill_kernel, dim3(n_tiles), dim3(qpf * frames), 0, st, t_utt, t_n0, t_cnt, p->d_frame_off, p->d_utt_seed, call, S, p->NT,
+                     qpf, p->Lp, eps_out, u_out);
   VN_CHECK_HIP(hipGetLastError());
   return 0;
+}
+// a wide plan draws per 16-frame wave tile, 32 quads of 128 latents: [S][NT][128]
+int vn_launch_wide_rng_fill(vaenmf_plan* p, uint32_t call, int S, float* eps_out, float* u_out, hipStream_t st) {
+  return launch_rng_fill(p, p->n_wtiles, 16, p->d_wt_utt, p->d_wt_n0, p->d_wt_cnt, call, S, eps_out, u_out, st);
+}
+
+extern "C" int vaenmf_rng_fill(vaenmf_plan* p, uint32_t call, int32_t S, float* eps_out, float* u_out, void* stream) {
+  if (int e = check_bound(p)) return e;
+  if (p->wide) return vn_launch_wide_rng_fill(p, call, S, eps_out, u_out, (hipStream_t)stream);
+  return launch_rng_fill(p, p->n_tiles, p->tile_frames, p->d_tile_utt, p->d_tile_n0, p->d_tile_cnt, call, S, eps_out, u_out, (hipStream_t)stream);   // team tiles, 8 quads of 32
 }
 
 extern "C" int vaenmf_decode(vaenmf_plan* p, const float* Zs, int32_t Rcap, int32_t R, const float* B1, float* Vs_out, void* stream) {
   if (int e = check_bound(p)) return e;
-  VN_REQUIRE(!p->wide, "%s: a wide decoder plan (z_dim > 32 or a hidden layer of 256 units) has no decoding kernels; run the chain with the sample "
-             "store on (vaenmf_sample_store) and use vaenmf_m_step_stored / vaenmf_wiener_stored (vaenmf_sample_store_gather for the variances)", "vaenmf_decode");
+  if (int e = require_narrow(p, "vaenmf_decode")) return e;
   VN_REQUIRE(R >= 1 && R <= Rcap, "bad R=%d (Rcap=%d)", R, Rcap);
   DecodeArgs a = base_decode_args(p, Zs, Rcap, R, B1);
   a.Vs_out = Vs_out;
@@ -1452,8 +1447,7 @@ extern "C" int vaenmf_decode(vaenmf_plan* p, const float* Zs, int32_t Rcap, int3
 extern "C" int vaenmf_m_step(vaenmf_plan* p, const float* X2, float* W, float* Ht, float* g, const float* Zs,
                              int32_t Rcap, int32_t R, const float* B1, double* cost_frames, void* stream) {
   if (int e = check_bound(p)) return e;
-  VN_REQUIRE(!p->wide, "%s: a wide decoder plan (z_dim > 32 or a hidden layer of 256 units) has no decoding kernels; run the chain with the sample "
-             "store on (vaenmf_sample_store) and use vaenmf_m_step_stored / vaenmf_wiener_stored (vaenmf_sample_store_gather for the variances)", "vaenmf_m_step");
+  if (int e = require_narrow(p, "vaenmf_m_step")) return e;
   VN_REQUIRE(R >= 1 && R <= Rcap, "bad R=%d (Rcap=%d)", R, Rcap);
   hipStream_t st = (hipStream_t)stream;
   DecodeArgs a = base_decode_args(p, Zs, Rcap, R, B1);
@@ -1476,8 +1470,7 @@ extern "C" int vaenmf_wiener(vaenmf_plan* p, const float* X2, const float* W, co
                              const float* Zs, int32_t Rcap, int32_t R, const float* B1, const float* X,
                              float* S_hat, float* N_hat, float* WFs, float* WFn, void* stream) {
   if (int e = check_bound(p)) return e;
-  VN_REQUIRE(!p->wide, "%s: a wide decoder plan (z_dim > 32 or a hidden layer of 256 units) has no decoding kernels; run the chain with the sample "
-             "store on (vaenmf_sample_store) and use vaenmf_m_step_stored / vaenmf_wiener_stored (vaenmf_sample_store_gather for the variances)", "vaenmf_wiener");
+  if (int e = require_narrow(p, "vaenmf_wiener")) return e;
   VN_REQUIRE(R >= 1 && R <= Rcap, "bad R=%d (Rcap=%d)", R, Rcap);
   DecodeArgs a = base_decode_args(p, Zs, Rcap, R, B1);
   a.X2 = X2; a.W = W; a.Ht = const_cast<float*>(Ht); a.g = const_cast<float*>(g); a.X = X;

@@ -33,27 +33,11 @@ struct WideArgs {
   int NT1, NT2, NT3;               // feature tiles of layer 1 (8 or 16), of layer 2 (0: one hidden layer, 8 or 16), bin tiles
   int NK1, NK2, NK3;               // k-steps: of layer 1 that hold latents, of layer 2 (H1 / 32), of the output layer (4 or 8)
   int H1, Lz, F, Fs, Kp, NT;
-  const float *X2, *W, *Ht, *g, *B1, *Vb;
-  float *Z, *Zs, *acc_out;
-  void* VsS; int32_t* src; int Rs;
-  VnStoreLayout lay;               // of VsS (common.h)
+  VnChainCall cc;                  // the call (common.h): its buffers, the store and its layout, the replay draws, counts, step size
+  const float* Vb;                 // the plan's fixed noise variance [NT][Fs] or null: Vb = W H
   const int32_t *wt_utt, *wt_n0, *wt_cnt, *frame_off;
   const uint64_t* utt_seed;
-  const float *eps, *u;
-  int Rcap, nsamples, burnin, rng_mode, update_Z;
-  uint32_t call;
-  float sd;
 };
-
-template <bool SPLIT>
-__device__ __forceinline__ void wd_split8(const float (&z)[8], bf16x8& hi, bf16x8& lo) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const __bf16 h = (__bf16)z[j];
-    hi[j] = h;
-    lo[j] = SPLIT ? (__bf16)(z[j] - (float)h) : (__bf16)0.f;
-  }
-}
 
 template <bool SPLIT, bool STORE>
 __global__ __launch_bounds__(256) void widechain_kernel(const WideArgs a) {
@@ -67,6 +51,7 @@ __global__ __launch_bounds__(256) void widechain_kernel(const WideArgs a) {
   __shared__ float ppart[4][16];             // partial prior term
   __shared__ float ush[16];                  // the step's uniform per frame
 
+  const VnChainCall& cc = a.cc;
   const int lane = threadIdx.x & 63, q = lane >> 4, c = lane & 15;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const unsigned lane16 = lane * 16;
@@ -75,61 +60,20 @@ __global__ __launch_bounds__(256) void widechain_kernel(const WideArgs a) {
   // columns behind the tile's last frame shadow it (same inputs, same noise) and store nothing
   const bool fvalid = c < cnt;
   const int nrow = n0 + (fvalid ? c : cnt - 1);
-  const float gn = a.g[nrow];
+  const float gn = cc.g[nrow];
 
+  // the fragment loaders and the activation store: this kernel's address arithmetic, then common.h's load_frag / store_act_tile
   auto wfrag = [&](const __bf16* base, int t, int nk, int s, bf16x8& hi, bf16x8& lo) {
-    const char* p = reinterpret_cast<const char*>(base) + ((size_t)(t * nk + s) * 2) * 1024 + lane16;
-    hi = *reinterpret_cast<const bf16x8*>(p);
-    if (SPLIT) lo = *reinterpret_cast<const bf16x8*>(p + 1024); else lo = hi;
+    load_frag<SPLIT>(reinterpret_cast<const char*>(base) + ((size_t)(t * nk + s) * 2) * 1024 + lane16, hi, lo);
   };
-  auto afrag = [&](const char* img, int s, bf16x8& hi, bf16x8& lo) {
-    const char* p = img + s * PARTS * 1024 + lane16;
-    hi = *reinterpret_cast<const bf16x8*>(p);
-    if (SPLIT) lo = *reinterpret_cast<const bf16x8*>(p + 1024); else lo = hi;
-  };
-  // tanh, split and store feature tile t into an image: tile t is half (t & 1) of k-step t >> 1
-  auto store_act = [&](char* img, int t, const f32x4 acc) {
-    bf16x4 hi, lo;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float h = fast_tanh(acc[k]);
-      const __bf16 x = (__bf16)h;
-      hi[k] = x;
-      lo[k] = (__bf16)(h - (float)x);
-    }
-    char* p = img + (t >> 1) * PARTS * 1024 + lane16 + (t & 1) * 8;
-    *reinterpret_cast<bf16x4*>(p) = hi;
-    if (SPLIT) *reinterpret_cast<bf16x4*>(p + 1024) = lo;
-  };
+  auto afrag = [&](const char* img, int s, bf16x8& hi, bf16x8& lo) { load_frag<SPLIT>(img + s * PARTS * 1024 + lane16, hi, lo); };
+  auto store_act = [&](char* img, int t, const f32x4 acc) { store_act_tile<SPLIT>(img, lane16, t, acc); };
 
-  // ---- per-(bin, frame) constants in accumulator layout: X2 and Vb = W H (mcem.py:81-82) or the caller's Vb.
-  // Padding bins: X2 = 0, Vb = 1, Vs = 0: their term is exactly 0.
+  // ---- per-(bin, frame) constants in accumulator layout: X2 and Vb = W H, padding bins X2 = 0, Vb = 1 (tile_consts4)
   f32x4 x2[WD_MAXT], vb[WD_MAXT];
 #pragma unroll
-  for (int i = 0; i < WD_MAXT; ++i) {
-    const int t = w + 4 * i, f0 = 16 * t + 4 * q;
-    f32x4 xv = {0, 0, 0, 0}, v = {0, 0, 0, 0};
-    if (t < a.NT3) {
-      xv = *reinterpret_cast<const f32x4*>(a.X2 + (size_t)nrow * a.Fs + f0);
-      if (a.Vb) {
-        v = *reinterpret_cast<const f32x4*>(a.Vb + (size_t)nrow * a.Fs + f0);
-      } else {
-        for (int k = 0; k < a.Kp; k += 4) {
-          const f32x4 h = *reinterpret_cast<const f32x4*>(a.Ht + (size_t)nrow * a.Kp + k);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const f32x4 wr = *reinterpret_cast<const f32x4*>(a.W + ((size_t)utt * a.Fs + f0 + r) * a.Kp + k);
-            v[r] += wr[0] * h[0] + wr[1] * h[1] + wr[2] * h[2] + wr[3] * h[3];
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      if (f0 + r >= a.F) { xv[r] = 0.f; v[r] = 1.f; }
-    x2[i] = xv;
-    vb[i] = v;
-  }
+  for (int i = 0; i < WD_MAXT; ++i)
+    tile_consts4(w + 4 * i < a.NT3, cc.X2, a.Vb, cc.W, cc.Ht, a.Fs, a.Kp, nrow, utt, 16 * (w + 4 * i) + 4 * q, a.F, x2[i], vb[i]);
   // ---- accumulator init of the hidden layers: b1, or per frame b1 + W1y y_n (M2, vaenmf_layer1_bias); b2
   f32x4 bias1[4], bias2[4];
 #pragma unroll
@@ -137,7 +81,7 @@ __global__ __launch_bounds__(256) void widechain_kernel(const WideArgs a) {
     const int f0 = 16 * (w + 4 * i) + 4 * q;
     bias1[i] = f32x4{0, 0, 0, 0};
     if (w + 4 * i < a.NT1)
-      bias1[i] = a.B1 ? *reinterpret_cast<const f32x4*>(a.B1 + (size_t)nrow * a.H1 + f0) : *reinterpret_cast<const f32x4*>(a.b1 + f0);
+      bias1[i] = cc.B1 ? *reinterpret_cast<const f32x4*>(cc.B1 + (size_t)nrow * a.H1 + f0) : *reinterpret_cast<const f32x4*>(a.b1 + f0);
   }
 #pragma unroll
   for (int i = 0; i < 4; ++i)
@@ -145,20 +89,15 @@ __global__ __launch_bounds__(256) void widechain_kernel(const WideArgs a) {
   // ---- this lane's latents of its frame, fragment order of k-step w: 32 w + 4 q + (0..3) and 32 w + 16 + 4 q + (0..3)
   const int l0 = 32 * w + 4 * q, l1 = l0 + 16;
   float z[8];
-  {
-    const f32x4 lo = *reinterpret_cast<const f32x4*>(a.Z + (size_t)nrow * WD_LP + l0);
-    const f32x4 hi = *reinterpret_cast<const f32x4*>(a.Z + (size_t)nrow * WD_LP + l1);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { z[k] = lo[k]; z[4 + k] = hi[k]; }
-  }
+  load_row8(cc.Z + (size_t)nrow * WD_LP, l0, l1, z);
   // ---- noise: latent quads l0 / 4 and l1 / 4 of the frame; quads of padding latents (>= Lz) get none
   const bool on0 = l0 < a.Lz, on1 = l1 < a.Lz;
   Xs128 st0 = {1, 0, 0, 0}, st1 = {1, 0, 0, 0};
-  if (a.rng_mode == VAENMF_RNG_DEVICE) {
+  if (cc.rng_mode == VAENMF_RNG_DEVICE) {
     const uint64_t seed = a.utt_seed[utt];
     const uint32_t fr = (uint32_t)(nrow - a.frame_off[utt]);
-    if (on0) st0 = xs_seed(seed, fr, (uint32_t)(l0 >> 2), a.call);
-    if (on1) st1 = xs_seed(seed, fr, (uint32_t)(l1 >> 2), a.call);
+    if (on0) st0 = xs_seed(seed, fr, (uint32_t)(l0 >> 2), cc.call);
+    if (on1) st1 = xs_seed(seed, fr, (uint32_t)(l1 >> 2), cc.call);
   }
   const bool ulane = w == 0 && q == 0;      // quad 0 of the frame: its stream also yields the step's uniform
 
@@ -168,7 +107,7 @@ __global__ __launch_bounds__(256) void widechain_kernel(const WideArgs a) {
     constexpr bool DOST = STORE && decltype(dost)::value;
     {
       bf16x8 hi, lo;
-      wd_split8<SPLIT>(zz, hi, lo);
+      split8<SPLIT>(zz, hi, lo);
       *reinterpret_cast<bf16x8*>(zimg + w * PARTS * 1024 + lane16) = hi;
       if (SPLIT) *reinterpret_cast<bf16x8*>(zimg + w * PARTS * 1024 + 1024 + lane16) = lo;
     }
@@ -209,7 +148,7 @@ __global__ __launch_bounds__(256) void widechain_kernel(const WideArgs a) {
     }
     // ---- output layer and the frame's energy
     const char* last = a.NT2 > 0 ? act2 : act1;
-    char* const vrow = DOST ? reinterpret_cast<char*>(a.VsS) + ((size_t)nrow * a.lay.frame + (size_t)slot * a.lay.row) * sizeof(store_t) : nullptr;
+    char* const vrow = DOST ? reinterpret_cast<char*>(cc.VsS) + ((size_t)nrow * cc.lay.frame + (size_t)slot * cc.lay.row) * sizeof(store_t) : nullptr;
     double e = 0.0;
 #pragma unroll
     for (int i = 0; i < WD_MAXT; ++i) {
@@ -231,9 +170,9 @@ __global__ __launch_bounds__(256) void widechain_kernel(const WideArgs a) {
           pl += fast_log2(vx);
           px += x2[i][k] * fast_rcp(vx);
         }
-        if (DOST && fvalid && 16 * t + 4 * q >= (int)a.lay.row) {      // line-aligned layout: a row ends at bin F-2, bin F-1 has its own block
+        if (DOST && fvalid && 16 * t + 4 * q >= (int)cc.lay.row) {      // line-aligned layout: a row ends at bin F-2, bin F-1 has its own block
           if (16 * t + 4 * q == a.F - 1)
-            reinterpret_cast<store_t*>(a.VsS)[a.lay.xbase + (size_t)nrow * a.lay.xframe + (size_t)slot * a.lay.xslot] = (store_t)ev[0];
+            reinterpret_cast<store_t*>(cc.VsS)[cc.lay.xbase + (size_t)nrow * cc.lay.xframe + (size_t)slot * cc.lay.xslot] = (store_t)ev[0];
         } else if (DOST && fvalid) {
           store_t* dst = reinterpret_cast<store_t*>(vrow) + 16 * t + 4 * q;
           if (SPLIT) *reinterpret_cast<f32x4*>(dst) = ev;
@@ -253,31 +192,31 @@ __global__ __launch_bounds__(256) void widechain_kernel(const WideArgs a) {
   };
 
   double Ecur = 0.0;
-  int cur_src = a.nsamples;
+  int cur_src = cc.nsamples;
   // the passes of vn_chain_pass (common.h)
-  const int n_it = vn_chain_passes<STORE>(a.nsamples, a.burnin);
+  const int n_it = vn_chain_passes<STORE>(cc.nsamples, cc.burnin);
   for (int it = -1; it < n_it; ++it) {
-    const VnChainPass ps = vn_chain_pass<STORE>(it, a.nsamples, a.burnin);
+    const VnChainPass ps = vn_chain_pass<STORE>(it, cc.nsamples, cc.burnin);
     const bool re = ps.re, step = ps.step;
     const int m = ps.m, slot = ps.slot;
     // ---- proposal  Z' = Z + sqrt(var) * randn   (mcem.py:407)
     float e8[8] = {0, 0, 0, 0, 0, 0, 0, 0}, uu = 1.f;
     if (step) {
       f32x4 e0 = {0, 0, 0, 0}, e1 = {0, 0, 0, 0};
-      if (a.rng_mode == VAENMF_RNG_DEVICE) {
+      if (cc.rng_mode == VAENMF_RNG_DEVICE) {
         if (on0) e0 = normal4(st0);
         if (on1) e1 = normal4(st1);
         if (ulane) uu = uniform01(st0);
       } else {
         const size_t row = (size_t)m * a.NT + nrow;
-        if (on0) e0 = *reinterpret_cast<const f32x4*>(a.eps + row * WD_LP + l0);
-        if (on1) e1 = *reinterpret_cast<const f32x4*>(a.eps + row * WD_LP + l1);
-        if (ulane) uu = a.u[row];
+        if (on0) e0 = *reinterpret_cast<const f32x4*>(cc.eps + row * WD_LP + l0);
+        if (on1) e1 = *reinterpret_cast<const f32x4*>(cc.eps + row * WD_LP + l1);
+        if (ulane) uu = cc.u[row];
       }
 #pragma unroll
       for (int k = 0; k < 4; ++k) { e8[k] = e0[k]; e8[4 + k] = e1[k]; }
     }
-    const float sd = step ? a.sd : 0.f;
+    const float sd = step ? cc.sd : 0.f;
     float zp[8], pr = 0.f;                              // .5 * sum(Z^2 - Z'^2) follows (mcem.py:417)
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -291,42 +230,19 @@ __global__ __launch_bounds__(256) void widechain_kernel(const WideArgs a) {
     if (re) continue;                                   // (the state and its energy are untouched)
     const float accp = (float)(Ecur - Ep) + 0.5f * P;   // mcem.py:415-417
     const bool ok = m < 0 || fast_log(U) < accp;        // mcem.py:420
-    if (a.acc_out && m >= 0 && ulane && fvalid) a.acc_out[(size_t)m * a.NT + nrow] = accp;
+    if (cc.acc_out && m >= 0 && ulane && fvalid) cc.acc_out[(size_t)m * a.NT + nrow] = accp;
     if (ok) {                                           // mcem.py:429-433
 #pragma unroll
       for (int j = 0; j < 8; ++j) z[j] = zp[j];
       Ecur = Ep;
-      if (STORE && m >= a.burnin) cur_src = m - a.burnin;
+      if (STORE && m >= cc.burnin) cur_src = m - cc.burnin;
     }
-    if (m >= a.burnin && fvalid) {
-      if (STORE && w == 1 && q == 0) a.src[(size_t)(m - a.burnin) * a.NT + nrow] = cur_src;
-      if (a.Zs) {                                       // mcem.py:435-437
-        float* dst = a.Zs + ((size_t)nrow * a.Rcap + (m - a.burnin)) * WD_LP;
-        *reinterpret_cast<f32x4*>(dst + l0) = f32x4{z[0], z[1], z[2], z[3]};
-        *reinterpret_cast<f32x4*>(dst + l1) = f32x4{z[4], z[5], z[6], z[7]};
-      }
+    if (m >= cc.burnin && fvalid) {
+      if (STORE && w == 1 && q == 0) cc.src[(size_t)(m - cc.burnin) * a.NT + nrow] = cur_src;
+      if (cc.Zs) store_row8(cc.Zs + ((size_t)nrow * cc.Rcap + (m - cc.burnin)) * WD_LP, l0, l1, z);    // mcem.py:435-437
     }
   }
-  if (a.update_Z && fvalid) {                           // self.Z = last draw (mcem.py:466)
-    float* dst = a.Z + (size_t)nrow * WD_LP;
-    *reinterpret_cast<f32x4*>(dst + l0) = f32x4{z[0], z[1], z[2], z[3]};
-    *reinterpret_cast<f32x4*>(dst + l1) = f32x4{z[4], z[5], z[6], z[7]};
-  }
-}
-
-// the streams of widechain_kernel written to global memory (vaenmf_rng_fill on a wide plan): thread <-> (frame, quad)
-__global__ void wide_rng_fill_kernel(const int32_t* wt_utt, const int32_t* wt_n0, const int32_t* wt_cnt, const int32_t* frame_off,
-                                     const uint64_t* utt_seed, uint32_t call, int S, int NT, float* eps_out, float* u_out) {
-  const int tile = blockIdx.x, sfr = threadIdx.x >> 5, squad = threadIdx.x & 31;
-  const int utt = wt_utt[tile], n0 = wt_n0[tile], cnt = wt_cnt[tile];
-  if (sfr >= cnt) return;
-  Xs128 st = xs_seed(utt_seed[utt], (uint32_t)(n0 - frame_off[utt] + sfr), (uint32_t)squad, call);
-  for (int s = 0; s < S; ++s) {
-    const f32x4 e = normal4(st);
-    const size_t row = (size_t)s * NT + n0 + sfr;
-    *reinterpret_cast<f32x4*>(eps_out + row * WD_LP + 4 * squad) = e;
-    if (squad == 0) u_out[row] = uniform01(st);
-  }
+  if (cc.update_Z && fvalid) store_row8(cc.Z + (size_t)nrow * WD_LP, l0, l1, z);    // self.Z = last draw (mcem.py:466)
 }
 
 }  // namespace
@@ -341,30 +257,20 @@ int vn_launch_widechain(vaenmf_plan* p, const VnChainCall& cc, hipStream_t st) {
   VN_REQUIRE(a.NT3 <= 4 * WD_MAXT && a.NT1 <= 16 && a.NT2 <= 16 && a.NK2 <= 8 && a.NK3 <= 8 && a.NK1 <= 4 && p->Lp == WD_LP,
              "wide chain: shape outside the kernel's tiles");
   a.F = p->cfg.F; a.Fs = p->Fs; a.Kp = p->Kp; a.NT = p->NT;
-  a.X2 = cc.X2; a.W = cc.W; a.Ht = cc.Ht; a.g = cc.g; a.B1 = cc.B1; a.Vb = p->Vb_ext;
-  a.Z = cc.Z; a.Zs = cc.Zs; a.acc_out = cc.acc_out;
-  a.VsS = cc.VsS; a.src = cc.src; a.Rs = cc.Rs; a.lay = cc.lay;
+  a.cc = cc;
+  a.Vb = p->Vb_ext;
   a.wt_utt = p->d_wt_utt; a.wt_n0 = p->d_wt_n0; a.wt_cnt = p->d_wt_cnt; a.frame_off = p->d_frame_off;
-  a.utt_seed = p->d_utt_seed; a.eps = cc.eps; a.u = cc.u;
-  a.Rcap = cc.Rcap; a.nsamples = cc.nsamples; a.burnin = cc.burnin; a.rng_mode = cc.rng_mode; a.update_Z = cc.update_Z;
-  a.call = cc.call; a.sd = cc.sd;
+  a.utt_seed = p->d_utt_seed;
   const bool split = p->cfg.precision == VAENMF_PREC_BF16X3;
   const dim3 grid(p->n_wtiles), blk(256);
   if (split) {
-    if (a.VsS) hipLaunchKernelGGL((widechain_kernel<true, true>), grid, blk, 0, st, a);
+    if (cc.VsS) hipLaunchKernelGGL((widechain_kernel<true, true>), grid, blk, 0, st, a);
     else hipLaunchKernelGGL((widechain_kernel<true, false>), grid, blk, 0, st, a);
   } else {
-    if (a.VsS) hipLaunchKernelGGL((widechain_kernel<false, true>), grid, blk, 0, st, a);
+    if (cc.VsS) hipLaunchKernelGGL((widechain_kernel<false, true>), grid, blk, 0, st, a);
     else hipLaunchKernelGGL((widechain_kernel<false, false>), grid, blk, 0, st, a);
   }
   VN_CHECK_HIP(hipGetLastError());
   p->last_chain_kernel = 3;
-  return 0;
-}
-
-int vn_launch_wide_rng_fill(vaenmf_plan* p, uint32_t call, int S, float* eps_out, float* u_out, hipStream_t st) {
-  hipLaunchKernelGGL(wide_rng_fill_kernel, dim3(p->n_wtiles), dim3(16 * 32), 0, st, p->d_wt_utt, p->d_wt_n0, p->d_wt_cnt,
-                     p->d_frame_off, p->d_utt_seed, call, S, p->NT, eps_out, u_out);
-  VN_CHECK_HIP(hipGetLastError());
   return 0;
 }

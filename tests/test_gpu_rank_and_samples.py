@@ -110,7 +110,7 @@ def stream_class(F, K, R, precision, variant, n_wave_tiles, n_cus=256, wfused=Tr
 
 
 def decode_class(F, K, R, precision):
-    """engine.hip: launch_decode / launch_decode_kp and decode_kernel's loop over chunks of 32 samples."""
+    """engine.hip: launch_decode (with_geom, then the rank) and decode_kernel's loop over chunks of 32 samples."""
     sc = shape_class(F, K, precision, N_WAVE_TILES)
     m = R % 32
     return dict(geom=sc["geom"], split=precision == "bf16x3", KP=sc["Kp"], chunks=(R + 31) // 32,
