@@ -11,7 +11,7 @@ The checkpoints are state_dicts in the reference's key layout: they load with st
 they are into pipeline.Reconstructor and engine.classifier_layers_from_state.
 
 There is no CPU fallback: a Trainer needs the HIP library and a GPU.  Host-only (no library): model_spec, state_keys,
-checkpoint_name, batch_bounds, epoch_log_lines.
+state_shapes, check_adam_state, checkpoint_name, batch_bounds, epoch_log_lines.
 
 Not built: Classifier(batch_norm=True), Classifier2Classes, the MSE losses of training_wiener_filter.py, U_loss, the HDF5
 loader, data-parallel training -- NotImplementedError where reachable."""
@@ -74,6 +74,41 @@ def state_keys(kind, n_hidden):
         return sum([wb("hidden.%d" % i) for i in range(n_hidden)], []) + wb("output_layer")
     return (sum([wb("encoder.hidden.%d" % i) for i in range(n_hidden)], []) + wb("encoder.sample.mu") + wb("encoder.sample.log_var") +
             sum([wb("decoder.hidden.%d" % i) for i in range(n_hidden)], []) + wb("decoder.reconstruction"))
+
+
+def state_shapes(spec):
+    """The trained tensors' shapes in state_keys' order: what vaenmf_trainer_tensor_shape reports, without the library."""
+    wb = lambda out, n_in: [(out, n_in), (out,)]
+    h = list(spec.hidden)
+    if spec.kind == "Classifier":
+        widths = [spec.x_dim] + h + [spec.y_dim]
+        return sum([wb(o, i) for i, o in zip(widths, widths[1:])], [])
+    enc, dec = [spec.x_dim + spec.y_dim] + h, [spec.z_dim + spec.y_dim] + h[::-1] + [spec.x_dim]
+    return (sum([wb(o, i) for i, o in zip(enc, enc[1:])], []) + 2 * wb(spec.z_dim, enc[-1]) +
+            sum([wb(o, i) for i, o in zip(dec, dec[1:])], []))
+
+
+def check_adam_state(state, keys, shapes):
+    """What Trainer.load_adam_state takes: dict(step, exp_avg, exp_avg_sq) as Trainer.adam_state returns it, the two moment
+    dicts with exactly the trained tensors' keys and shapes, step in [0, 2^31 - 1).  Returns the step.  Pure."""
+    if not isinstance(state, dict) or set(state) != {"step", "exp_avg", "exp_avg_sq"}:
+        got = sorted(state, key=str) if isinstance(state, dict) else type(state).__name__
+        raise KeyError("an Adam state is dict(step, exp_avg, exp_avg_sq); got %s" % (got,))
+    step = state["step"]
+    try:
+        whole = not isinstance(step, bool) and int(step) == step and 0 <= int(step) < 2 ** 31 - 1
+    except (TypeError, ValueError, OverflowError):
+        whole = False
+    if not whole:
+        raise ValueError("step=%r is not a whole number in [0, 2^31 - 1)" % (step,))
+    for name in ("exp_avg", "exp_avg_sq"):
+        if not isinstance(state[name], dict) or set(state[name]) != set(keys):
+            raise KeyError("%s must hold exactly the trained tensors %s" % (name, list(keys)))
+        for k, shp in zip(keys, shapes):
+            got = tuple(np.shape(state[name][k]))          # a tensor, an array or nested lists
+            if got != tuple(shp):
+                raise ValueError("%s[%s] has shape %s, the model %s" % (name, k, got, tuple(shp)))
+    return int(step)
 
 
 def checkpoint_name(kind, epoch, vloss):
@@ -190,14 +225,26 @@ class Trainer:
         missing = [k for k in self.keys if k not in sd]
         if missing:
             raise KeyError("state_dict lacks %s" % missing)
+        self._set(_lib.TRAIN_PARAM, sd)
+
+    def _set(self, which, tensors):
         with torch.cuda.device(self.device):
             for i, (k, shp) in enumerate(zip(self.keys, self.shapes)):
-                v = torch.as_tensor(sd[k]).detach()
+                v = torch.as_tensor(tensors[k]).detach()
                 if tuple(v.shape) != tuple(shp):
                     raise ValueError("%s has shape %s, the model %s" % (k, tuple(v.shape), tuple(shp)))
                 t = v.to(device=self.device, dtype=torch.float32).contiguous()
-                check(lib().vaenmf_trainer_set_tensor(self._h, _lib.TRAIN_PARAM, i, _ptr(t), _stream()))
+                check(lib().vaenmf_trainer_set_tensor(self._h, which, i, _ptr(t), _stream()))
             torch.cuda.current_stream().synchronize()        # t is released when the loop moves on
+
+    def load_adam_state(self, state):
+        """Resume: `state` as adam_state() returns it.  Writes Adam's m and v and sets the step count, which is Adam's t and
+        the key of the draws the next steps make on the device; with load_state_dict before it, training goes on bit for
+        bit as if it had not stopped."""
+        step = check_adam_state(state, self.keys, self.shapes)
+        self._set(_lib.TRAIN_ADAM_M, state["exp_avg"])
+        self._set(_lib.TRAIN_ADAM_V, state["exp_avg_sq"])
+        check(lib().vaenmf_trainer_set_step_count(self._h, step))
 
     # ------------------------------------------------------------------ data
     def put(self, X, Y=None):

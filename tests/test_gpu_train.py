@@ -107,6 +107,57 @@ def _deriv64(name, y):
     return {"none": np.ones_like(y), "tanh": 1 - y * y, "relu": (y > 0).astype(np.float64), "exp": y, "sigmoid": y * (1 - y)}[name]
 
 
+def gemm_forms_case(rng, M, n_in, n_out, act, j, worst):
+    """Forward, dX, dW and db of one layer shape against float64, each element within its bound from the operands; the
+    largest error / bound of each form goes into `worst`.  (tests/test_gpu_train_shapes.py runs it at long reductions.)"""
+    ldx, ldw, ldy, ldz, ldp = n_in + 3, n_in + (j % 3), n_out + 5, n_out + 1, n_in + 2
+    X = rng.standard_normal((M, n_in)).astype(np.float32)
+    W = (rng.standard_normal((n_out, n_in)) / np.sqrt(n_in)).astype(np.float32)
+    b = (rng.standard_normal(n_out) * 0.3).astype(np.float32)
+    dZ = rng.standard_normal((M, n_out)).astype(np.float32)
+    dZ[rng.random((M, n_out)) < 0.05] = 0.0
+    Yp = _saved_output(rng, act, (M, n_in))
+    arena = Arena(8 << 20, "nan", device=DEV)
+    dX_, dW_, db_ = _put(arena, "X", X, ldx), _put(arena, "W", W, ldw), _put(arena, "b", b)
+    dZ_, Yp_ = _put(arena, "dZ", dZ, ldz), _put(arena, "Yp", Yp, ldp)
+    Y_ = _out(arena, "Y", M, n_out, ldy)
+    gX_ = _out(arena, "gX", M, n_in, ldx)
+    gW_ = _out(arena, "gW", n_out, n_in, ldw)
+    gb_ = _out(arena, "gb", n_out, 0)
+    arena.snapshot(["X", "W", "b", "dZ", "Yp"])
+    check(lib().vaenmf_train_dense_fwd(_p(dX_), M, n_in, ldx, _p(dW_), ldw, _p(db_), n_out, ACTS[act], _p(Y_), ldy, _st()))
+    check(lib().vaenmf_train_dense_dx(_p(dZ_), M, n_out, ldz, _p(dW_), ldw, n_in, _p(Yp_), ldp, ACTS[act], _p(gX_), ldx, _st()))
+    check(lib().vaenmf_train_dense_dw(_p(dZ_), M, n_out, ldz, _p(dX_), n_in, ldx, _p(gW_), ldw, _p(gb_), _st()))
+    torch.cuda.synchronize()
+    what = "M=%d in=%d out=%d act=%s" % (M, n_in, n_out, act)
+    arena.check(what)
+    arena.unchanged(what=what)
+    assert _padding_untouched(arena, Y_, n_out) and _padding_untouched(arena, gX_, n_in) and _padding_untouched(arena, gW_, n_in), what
+    X64, W64, dZ64 = X.astype(np.float64), W.astype(np.float64), dZ.astype(np.float64)
+    # forward
+    pre = X64 @ W64.T + b
+    tol = _act_tol(act, pre, C_CHAIN * (np.abs(X64) @ np.abs(W64).T + np.abs(b)))
+    err = np.abs(Y_[:, :n_out].cpu().numpy().astype(np.float64) - _act64(act, pre))
+    assert np.all(err <= tol), (what, "fwd", float((err / tol).max()))
+    worst["fwd"] = max(worst["fwd"], float((err / tol).max()))
+    # data gradient
+    acc, d = dZ64 @ W64, _deriv64(act, Yp)
+    ref = acc * d
+    tol = C_CHAIN * (np.abs(dZ64) @ np.abs(W64)) * np.abs(d) + 2 * U * np.abs(acc) + 2 * U * np.abs(ref)
+    err = np.abs(gX_[:, :n_in].cpu().numpy().astype(np.float64) - ref)
+    assert np.all(err <= tol), (what, "dx", float((err / np.maximum(tol, 1e-300)).max()))
+    worst["dx"] = max(worst["dx"], float((err / np.maximum(tol, 1e-300)).max()))
+    # weight gradient and bias gradient from the same pass
+    ref, tol = dZ64.T @ X64, C_CHAIN * (np.abs(dZ64).T @ np.abs(X64))
+    err = np.abs(gW_[:, :n_in].cpu().numpy().astype(np.float64) - ref)
+    assert np.all(err <= tol), (what, "dw", float((err / np.maximum(tol, 1e-300)).max()))
+    worst["dw"] = max(worst["dw"], float((err / np.maximum(tol, 1e-300)).max()))
+    ref, tol = dZ64.sum(0), C_CHAIN * np.abs(dZ64).sum(0)
+    err = np.abs(gb_.cpu().numpy().astype(np.float64) - ref)
+    assert np.all(err <= tol), (what, "db", float((err / np.maximum(tol, 1e-300)).max()))
+    worst["db"] = max(worst["db"], float((err / np.maximum(tol, 1e-300)).max()))
+
+
 @pytest.mark.parametrize("M", SIZES_M)
 def test_gemm_forms(M):
     rng = np.random.default_rng(700 + M)
@@ -115,52 +166,7 @@ def test_gemm_forms(M):
     for i, n_in in enumerate(SIZES_IO):
         for j, n_out in enumerate(SIZES_IO):
             act = names[(i * len(SIZES_IO) + j) % len(names)]
-            ldx, ldw, ldy, ldz, ldp = n_in + 3, n_in + (j % 3), n_out + 5, n_out + 1, n_in + 2
-            X = rng.standard_normal((M, n_in)).astype(np.float32)
-            W = (rng.standard_normal((n_out, n_in)) / np.sqrt(n_in)).astype(np.float32)
-            b = (rng.standard_normal(n_out) * 0.3).astype(np.float32)
-            dZ = rng.standard_normal((M, n_out)).astype(np.float32)
-            dZ[rng.random((M, n_out)) < 0.05] = 0.0
-            Yp = _saved_output(rng, act, (M, n_in))
-            arena = Arena(8 << 20, "nan", device=DEV)
-            dX_, dW_, db_ = _put(arena, "X", X, ldx), _put(arena, "W", W, ldw), _put(arena, "b", b)
-            dZ_, Yp_ = _put(arena, "dZ", dZ, ldz), _put(arena, "Yp", Yp, ldp)
-            Y_ = _out(arena, "Y", M, n_out, ldy)
-            gX_ = _out(arena, "gX", M, n_in, ldx)
-            gW_ = _out(arena, "gW", n_out, n_in, ldw)
-            gb_ = _out(arena, "gb", n_out, 0)
-            arena.snapshot(["X", "W", "b", "dZ", "Yp"])
-            check(lib().vaenmf_train_dense_fwd(_p(dX_), M, n_in, ldx, _p(dW_), ldw, _p(db_), n_out, ACTS[act], _p(Y_), ldy, _st()))
-            check(lib().vaenmf_train_dense_dx(_p(dZ_), M, n_out, ldz, _p(dW_), ldw, n_in, _p(Yp_), ldp, ACTS[act], _p(gX_), ldx, _st()))
-            check(lib().vaenmf_train_dense_dw(_p(dZ_), M, n_out, ldz, _p(dX_), n_in, ldx, _p(gW_), ldw, _p(gb_), _st()))
-            torch.cuda.synchronize()
-            what = "M=%d in=%d out=%d act=%s" % (M, n_in, n_out, act)
-            arena.check(what)
-            arena.unchanged(what=what)
-            assert _padding_untouched(arena, Y_, n_out) and _padding_untouched(arena, gX_, n_in) and _padding_untouched(arena, gW_, n_in), what
-            X64, W64, dZ64 = X.astype(np.float64), W.astype(np.float64), dZ.astype(np.float64)
-            # forward
-            pre = X64 @ W64.T + b
-            tol = _act_tol(act, pre, C_CHAIN * (np.abs(X64) @ np.abs(W64).T + np.abs(b)))
-            err = np.abs(Y_[:, :n_out].cpu().numpy().astype(np.float64) - _act64(act, pre))
-            assert np.all(err <= tol), (what, "fwd", float((err / tol).max()))
-            worst["fwd"] = max(worst["fwd"], float((err / tol).max()))
-            # data gradient
-            acc, d = dZ64 @ W64, _deriv64(act, Yp)
-            ref = acc * d
-            tol = C_CHAIN * (np.abs(dZ64) @ np.abs(W64)) * np.abs(d) + 2 * U * np.abs(acc) + 2 * U * np.abs(ref)
-            err = np.abs(gX_[:, :n_in].cpu().numpy().astype(np.float64) - ref)
-            assert np.all(err <= tol), (what, "dx", float((err / np.maximum(tol, 1e-300)).max()))
-            worst["dx"] = max(worst["dx"], float((err / np.maximum(tol, 1e-300)).max()))
-            # weight gradient and bias gradient from the same pass
-            ref, tol = dZ64.T @ X64, C_CHAIN * (np.abs(dZ64).T @ np.abs(X64))
-            err = np.abs(gW_[:, :n_in].cpu().numpy().astype(np.float64) - ref)
-            assert np.all(err <= tol), (what, "dw", float((err / np.maximum(tol, 1e-300)).max()))
-            worst["dw"] = max(worst["dw"], float((err / np.maximum(tol, 1e-300)).max()))
-            ref, tol = dZ64.sum(0), C_CHAIN * np.abs(dZ64).sum(0)
-            err = np.abs(gb_.cpu().numpy().astype(np.float64) - ref)
-            assert np.all(err <= tol), (what, "db", float((err / np.maximum(tol, 1e-300)).max()))
-            worst["db"] = max(worst["db"], float((err / np.maximum(tol, 1e-300)).max()))
+            gemm_forms_case(rng, M, n_in, n_out, act, j, worst)
     print("M=%d: worst error / bound %s" % (M, worst))
 
 

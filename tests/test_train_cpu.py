@@ -144,3 +144,89 @@ def test_unsupported_shapes_are_refused():
     with pytest.raises(NotImplementedError):
         vt._arrays("train.h5", True)
     assert vt.model_spec(vaenmf.VariationalAutoencoder([513, 16, [256]])).hidden == [256]
+
+
+# ---- unequal widths, schedules, the Adam state loader ---------------------------------------------------------------
+@pytest.mark.parametrize("name", sorted(tc.SHAPE_CASES))
+def test_shape_case_yardsticks_are_not_zero(name):
+    """The GPU tests divide by these: every tensor (tc.groups: every layer, where the biases have four elements) has a
+    float32 error against float64 that is neither zero nor beyond float32 rounding, and the weights moved."""
+    case = tc.SHAPE_CASES[name]
+    init, _, r64, r32 = tc.reference_runs(case)
+    assert list(r64.final) == list(tc.make_model(case).state_dict().keys())
+    assert (len(tc.groups(case)) < len(r64.final)) == (name == "m1_one_z4")     # per layer only where a tensor has < 8 elements
+    for label, keys in tc.groups(case):
+        eg, ep = nrm_err(tc.cat(r32.grad1, keys), tc.cat(r64.grad1, keys)), nrm_err(tc.cat(r32.final, keys), tc.cat(r64.final, keys))
+        print("%s %s: step-1 gradient %.3g, parameters after %d steps %.3g" % (name, label, eg, tc.STEPS, ep))
+        assert 0.0 < eg <= 1e-5, (label, eg)
+        assert 0.0 < ep <= 1e-4, (label, ep)
+    for k in r64.final:
+        if k.endswith("weight"):
+            assert np.abs(r64.final[k] - init[k].numpy()).max() > 1e-3, "the parameters did not move: the trajectory tests nothing"
+    ncol = 1 if case.kind == "Classifier" else 3
+    assert _loss_err(r32.losses[:, :ncol], r64.losses[:, :ncol]) > 0.0
+
+
+def test_constant_schedule_is_the_plain_case():
+    """The schedule form with the same batch size at every step draws the same data and runs the same steps, bit for bit."""
+    for name in ("m2_uneven", "clf_uneven"):
+        case = tc.SHAPE_CASES[name]
+        sched = case._replace(B=(case.B,) * tc.STEPS)
+        init, data, _, r32 = tc.reference_runs(case)
+        ds = tc.make_data(sched)
+        assert isinstance(ds["idx"], list) and np.array_equal(np.stack(ds["idx"]), data["idx"]) and np.array_equal(ds["X"], data["X"])
+        if data["eps"] is not None:
+            assert np.array_equal(np.stack(ds["eps"]), data["eps"])
+        got = tc.run_steps(sched, init, ds, torch.float32)
+        assert np.array_equal(got.losses, r32.losses) and np.array_equal(got.counts, r32.counts) and got.evals is None
+        for k in r32.final:
+            assert np.array_equal(got.final[k].view(np.int32), r32.final[k].view(np.int32)), k
+            assert np.array_equal(got.grad1[k].view(np.int32), r32.grad1[k].view(np.int32)), k
+
+
+@pytest.mark.parametrize("name", sorted(tc.SCHED_CASES))
+def test_scheduled_yardsticks(name):
+    """The ragged schedule with evaluations between its steps: the yardsticks the GPU test divides by are not zero, and an
+    evaluation takes part in nothing (the run without them ends in the same bits)."""
+    case = tc.SCHED_CASES[name]
+    init, data, evals, r64, r32 = tc.scheduled_runs(case)
+    assert [len(i) for i in data["idx"]] == list(tc.SCHED) and len(set(data["idx"][0].tolist())) < 128      # 128 of 96 rows repeat
+    assert r64.evals.shape == (len(tc.EVAL_AFTER), len(tc.EVAL_BATCHES), 3) and np.isfinite(r64.evals).all()
+    for label, keys in tc.groups(case):
+        assert 0.0 < nrm_err(tc.cat(r32.final, keys), tc.cat(r64.final, keys)) <= 1e-4, label
+    plain = tc.run_steps(case, init, data, torch.float32, len(tc.SCHED))
+    assert all(np.array_equal(plain.final[k].view(np.int32), r32.final[k].view(np.int32)) for k in r32.final)
+    assert np.array_equal(plain.losses, r32.losses)
+
+
+def test_adam_state_loader_checks():
+    for name in sorted(tc.SHAPE_CASES):
+        case = tc.SHAPE_CASES[name]
+        model = tc.make_model(case)
+        spec, keys = vt.model_spec(model), vt.state_keys(case.kind, len(case.hidden))
+        shapes = vt.state_shapes(spec)
+        assert shapes == [tuple(model.state_dict()[k].shape) for k in keys], name
+    zeros = lambda: {k: torch.zeros(s) for k, s in zip(keys, shapes)}
+    good = {"step": 9, "exp_avg": zeros(), "exp_avg_sq": zeros()}
+    assert vt.check_adam_state(good, keys, shapes) == 9
+    assert vt.check_adam_state(dict(good, step=0), keys, shapes) == 0
+    with pytest.raises(KeyError):
+        vt.check_adam_state({"step": 9, "exp_avg": zeros()}, keys, shapes)                      # no second moment
+    with pytest.raises(KeyError):
+        vt.check_adam_state(dict(good, max_exp_avg_sq=zeros()), keys, shapes)                    # amsgrad is not run
+    lacking = zeros()
+    del lacking[keys[-1]]
+    with pytest.raises(KeyError):
+        vt.check_adam_state(dict(good, exp_avg=lacking), keys, shapes)
+    with pytest.raises(KeyError):
+        vt.check_adam_state(dict(good, exp_avg_sq=dict(zeros(), extra=torch.zeros(1))), keys, shapes)
+    wrong = zeros()
+    wrong[keys[0]] = torch.zeros(shapes[0][::-1])                                                # the weight transposed
+    with pytest.raises(ValueError):
+        vt.check_adam_state(dict(good, exp_avg_sq=wrong), keys, shapes)
+    assert vt.check_adam_state(dict(good, exp_avg={k: v.tolist() for k, v in zeros().items()}), keys, shapes) == 9    # nested lists
+    with pytest.raises(ValueError):
+        vt.check_adam_state(dict(good, exp_avg=dict(zeros(), **{keys[1]: [0.0]})), keys, shapes)
+    for step in (-1, 2 ** 31 - 1, 1.5, True, "9", None, float("nan"), float("inf")):
+        with pytest.raises(ValueError):
+            vt.check_adam_state(dict(good, step=step), keys, shapes)

@@ -15,6 +15,7 @@ import vaenmf
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 STEPS, POOL, LOSS_EPS = 20, 96, 1e-8
+SMALL_TENSOR = 8
 
 Case = collections.namedtuple("Case", "name kind x_dim y_dim z_dim hidden B seed")
 GOLDEN_CASES = {
@@ -25,6 +26,22 @@ GOLDEN_CASES = {
     "train_clf_vad_f65": Case("train_clf_vad_f65", "Classifier", 65, 1, 0, (128, 128), 33, 105),
 }
 SWEEP_B = (1, 15, 16, 17, 33, 128)
+# Unequal widths, none a multiple of 16 (m2_wide: the widest decoder the engine runs), so that exchanging the two hidden
+# widths, a leading dimension from the wrong layer or a wrong [mu | logvar] offset changes numbers, and every product of a
+# step leaves a remainder in its 32 x 64 x 64 tile.
+SHAPE_CASES = {
+    "m1_uneven": Case("m1_uneven", "M1", 67, 0, 20, (72, 40), 33, 201),
+    "m2_uneven": Case("m2_uneven", "M2", 67, 3, 20, (72, 40), 33, 202),
+    "clf_uneven": Case("clf_uneven", "Classifier", 67, 67, 0, (72, 40), 33, 203),
+    "m2_wide": Case("m2_wide", "M2", 65, 65, 128, (256, 128), 17, 204),
+    "m1_one_z4": Case("m1_one_z4", "M1", 67, 0, 4, (40,), 33, 205),
+}
+# The schedule form: B is a tuple of batch sizes, one per step (a long batch, a short one, one row, ... on one trainer of
+# max_batch 128).  128 rows of a pool of 96 repeat some.  Evaluations run after the steps EVAL_AFTER on a second pool of
+# EVAL_POOL rows in the batches EVAL_BATCHES.
+SCHED = (128, 80, 1, 17, 128, 33, 15, 128, 16, 2) * 2
+EVAL_AFTER, EVAL_POOL, EVAL_BATCHES = (2, 5, 10, 13, 17, 20), 50, ((0, 40), (40, 50))
+SCHED_CASES = {k: SHAPE_CASES[k]._replace(name=k + "_sched", B=SCHED, seed=SHAPE_CASES[k].seed + 100) for k in ("m1_uneven", "m2_uneven", "clf_uneven")}
 
 
 def sweep_case(kind, B):
@@ -46,23 +63,62 @@ def make_model(case, module=vaenmf):
     return module.Classifier([case.x_dim, h, case.y_dim])        # nn.Linear's default init, as the reference leaves it
 
 
+def make_pool(rng, case, n):
+    """(X [n][x] float32, Y [n][y] float32 or None): n frames and their labels from rng."""
+    scale = np.exp(rng.normal(0.0, 1.0, (n, 1)) + rng.normal(0.0, 0.7, (1, case.x_dim)))
+    X = (rng.exponential(1.0, (n, case.x_dim)) * scale).astype(np.float32)
+    X[rng.random((n, case.x_dim)) < 0.02] = 0.0                          # silent bins: log(x + eps)
+    return X, ((rng.random((n, case.y_dim)) < 0.4).astype(np.float32) if case.kind != "M1" else None)
+
+
 def make_data(case, steps=STEPS):
     """dict(X [POOL][x] float32, Y [POOL][y] float32 or None, idx [steps][B] int32, eps [steps][B][z] float32 or None,
-    mean, std [x] float32 or None)."""
+    mean, std [x] float32 or None).  With a schedule (case.B a tuple of `steps` batch sizes) idx and eps are lists of
+    per-step arrays [B_s] and [B_s][z]; a constant schedule gives the arrays of the plain case, row for row."""
     rng = np.random.default_rng(case.seed)
-    scale = np.exp(rng.normal(0.0, 1.0, (POOL, 1)) + rng.normal(0.0, 0.7, (1, case.x_dim)))
-    X = (rng.exponential(1.0, (POOL, case.x_dim)) * scale).astype(np.float32)
-    X[rng.random((POOL, case.x_dim)) < 0.02] = 0.0                       # silent bins: log(x + eps)
-    d = {"X": X, "Y": None, "eps": None, "mean": None, "std": None}
-    if case.kind != "M1":
-        d["Y"] = (rng.random((POOL, case.y_dim)) < 0.4).astype(np.float32)
-    d["idx"] = np.stack([rng.choice(POOL, case.B, replace=case.B > POOL) for _ in range(steps)]).astype(np.int32)
-    if case.kind != "Classifier":
-        d["eps"] = rng.standard_normal((steps, case.B, case.z_dim)).astype(np.float32)
+    X, Y = make_pool(rng, case, POOL)
+    d = {"X": X, "Y": Y, "eps": None, "mean": None, "std": None}
+    if isinstance(case.B, tuple):
+        assert len(case.B) == steps, "a schedule names one batch size per step"
+        d["idx"] = [rng.choice(POOL, b, replace=b > POOL).astype(np.int32) for b in case.B]
+        if case.kind != "Classifier":
+            d["eps"] = [rng.standard_normal((b, case.z_dim)).astype(np.float32) for b in case.B]
     else:
+        d["idx"] = np.stack([rng.choice(POOL, case.B, replace=case.B > POOL) for _ in range(steps)]).astype(np.int32)
+        if case.kind != "Classifier":
+            d["eps"] = rng.standard_normal((steps, case.B, case.z_dim)).astype(np.float32)
+    if case.kind == "Classifier":
         d["mean"] = X.mean(0).astype(np.float32)
         d["std"] = X.std(0, ddof=1).astype(np.float32)
     return d
+
+
+def make_eval(case):
+    """The evaluations of a scheduled run: dict(X [EVAL_POOL][x], Y or None, after: step numbers, batches: row index arrays,
+    eps [len(after)][len(batches)] of [rows][z] or None).  A pool of its own with its own generator: make_data is as it was."""
+    rng = np.random.default_rng(case.seed + 7000)
+    X, Y = make_pool(rng, case, EVAL_POOL)
+    batches = [np.arange(lo, hi, dtype=np.int32) for lo, hi in EVAL_BATCHES]
+    eps = None
+    if case.kind != "Classifier":
+        eps = [[rng.standard_normal((len(b), case.z_dim)).astype(np.float32) for b in batches] for _ in EVAL_AFTER]
+    return {"X": X, "Y": Y, "after": EVAL_AFTER, "batches": batches, "eps": eps}
+
+
+def groups(case):
+    """[(label, [keys])]: what the whole-step tests compare as one vector.  A tensor each, except where a case has tensors of
+    a handful of elements (m1_one_z4: 4-element biases), whose float32 yardstick is a few rounding events and not a
+    statistic (sweep_case): there a layer's weight and bias are one concatenated vector.  A handful: fewer than
+    SMALL_TENSOR = 8 elements in the case's smallest tensor."""
+    keys = vaenmf.train.state_keys(case.kind, len(case.hidden))
+    shapes = vaenmf.train.state_shapes(vaenmf.train.Spec(case.kind, case.x_dim, case.y_dim, case.z_dim, list(case.hidden)))
+    if min(int(np.prod(s)) for s in shapes) < SMALL_TENSOR:
+        return [(w[:-len(".weight")], [w, b]) for w, b in zip(keys[0::2], keys[1::2])]
+    return [(k, [k]) for k in keys]
+
+
+def cat(tensors, keys):
+    return np.concatenate([np.asarray(tensors[k], np.float64).ravel() for k in keys])
 
 
 def state_of(model):
@@ -96,18 +152,23 @@ def forward_loss(case, p, x, y, eps, mean=None, std=None):
     return recon + kl, recon, kl
 
 
-Run = collections.namedtuple("Run", "losses counts grad1 final")
+Run = collections.namedtuple("Run", "losses counts grad1 final evals", defaults=(None,))
 
 
-def run_steps(case, init, data, dtype, steps=STEPS, lr=1e-3, betas=(0.9, 0.999), adam_eps=1e-8):
+def run_steps(case, init, data, dtype, steps=STEPS, lr=1e-3, betas=(0.9, 0.999), adam_eps=1e-8, evals=None):
     """`steps` training steps from the state `init`: Run(losses [steps][3] float64 (loss, recon, KL; classifier: loss, loss, 0),
-    counts [steps][4] (tp, tn, fp, fn), grad1 {key: step-1 gradient}, final {key: parameter})."""
+    counts [steps][4] (tp, tn, fp, fn), grad1 {key: step-1 gradient}, final {key: parameter}, evals).  data["idx"] and
+    data["eps"] are [steps][B] arrays or lists of per-step arrays (a schedule).  evals (make_eval): after each step it names,
+    forward and loss only, under no_grad, on each of its batches of its own pool -> Run.evals [len(after)][len(batches)][3]."""
     keys = vaenmf.train.state_keys(case.kind, len(case.hidden))
     p = {k: torch.as_tensor(init[k]).detach().to(dtype).clone().requires_grad_(True) for k in keys}
     opt = torch.optim.Adam(list(p.values()), lr=lr, betas=betas, eps=adam_eps)
     t = lambda a: None if a is None else torch.as_tensor(a).to(dtype)
     X, Y, mean, std = t(data["X"]), t(data["Y"]), t(data["mean"]), t(data["std"])
     losses, counts, grad1 = np.zeros((steps, 3)), np.zeros((steps, 4), np.int64), None
+    ev = None
+    if evals is not None:
+        ev, EX, EY = np.zeros((len(evals["after"]), len(evals["batches"]), 3)), t(evals["X"]), t(evals["Y"])
     for s in range(steps):
         idx = torch.as_tensor(data["idx"][s].astype(np.int64))
         x, y = X[idx], (Y[idx] if Y is not None else None)
@@ -124,7 +185,18 @@ def run_steps(case, init, data, dtype, steps=STEPS, lr=1e-3, betas=(0.9, 0.999),
         if s == 0:
             grad1 = {k: v.grad.detach().clone().numpy() for k, v in p.items()}
         opt.step()
-    return Run(losses, counts, grad1, {k: v.detach().numpy() for k, v in p.items()})
+        if ev is not None and s + 1 in evals["after"]:
+            a = evals["after"].index(s + 1)
+            with torch.no_grad():
+                for j, rows in enumerate(evals["batches"]):
+                    r = torch.as_tensor(rows.astype(np.int64))
+                    y = EY[r] if EY is not None else None
+                    if case.kind == "Classifier":
+                        l = forward_loss(case, p, EX[r], y, None, mean, std)[0].item()
+                        ev[a, j] = [l, l, 0.0]
+                    else:
+                        ev[a, j] = [v.item() for v in forward_loss(case, p, EX[r], y, t(evals["eps"][a][j]))]
+    return Run(losses, counts, grad1, {k: v.detach().numpy() for k, v in p.items()}, ev)
 
 
 _CACHE = {}
@@ -136,6 +208,16 @@ def reference_runs(case, steps=STEPS):
     if key not in _CACHE:
         init, data = state_of(make_model(case)), make_data(case, steps)
         _CACHE[key] = (init, data, run_steps(case, init, data, torch.float64, steps), run_steps(case, init, data, torch.float32, steps))
+    return _CACHE[key]
+
+
+def scheduled_runs(case):
+    """(init, data, evals, float64 run, float32 run) of a scheduled case with its evaluations, computed once per process."""
+    key = (case, "sched")
+    if key not in _CACHE:
+        init, data, evals = state_of(make_model(case)), make_data(case, len(case.B)), make_eval(case)
+        _CACHE[key] = (init, data, evals, run_steps(case, init, data, torch.float64, len(case.B), evals=evals),
+                       run_steps(case, init, data, torch.float32, len(case.B), evals=evals))
     return _CACHE[key]
 
 
