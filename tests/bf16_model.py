@@ -25,6 +25,8 @@ from types import SimpleNamespace
 
 import numpy as np
 
+from em_support import dec_list  # noqa: F401  (the decoder's layer list, for the callers of prepare())
+
 f32, f64 = np.float32, np.float64
 LOG2E = 1.4426950408889634
 LN2 = 0.6931471805599453
@@ -389,14 +391,6 @@ CHAIN_NS, CHAIN_BURNIN, VAR_RW = 4, 2, 0.01
 def case_params(F, z_dim=32, h_dim=(128, 128), Dy=0):
     import vaenmf_oracle as orc
     return orc.xavier_normal_params([F, z_dim, list(h_dim)], seed=3, y_dim=Dy, bias_std=0.1)
-
-
-def dec_list(params):
-    n = 0
-    while "decoder.hidden.%d.weight" % n in params:
-        n += 1
-    keys = ["decoder.hidden.%d.%s" % (i, k) for i in range(n) for k in ("weight", "bias")]
-    return [params[k] for k in keys + ["decoder.reconstruction.weight", "decoder.reconstruction.bias"]]
 
 
 def decode_inputs(F, z_dim, Dy, Lp=32):

@@ -9,7 +9,7 @@ from collections import namedtuple
 import numpy as np
 
 import vaenmf_oracle as orc
-from test_gpu_bin_counts import shape_class
+from dispatch_model import shape_class
 
 COUNTS = [17, 1, 30, 5]
 ONE_TILE = [3]

@@ -187,8 +187,8 @@ def power_spec(eng):
 
 
 def make_guarded_engine(arena, params, F, K, counts, Rcap, precision="bf16x3", seeds=None):
-    """tests/wide_cases.make_engine on an arena: exact buffers (max_frames = NT, max_utts = U), poisoned free padding."""
-    from wide_cases import dec_list
+    """tests/em_support.make_engine on an arena: exact buffers (max_frames = NT, max_utts = U), poisoned free padding."""
+    from em_support import dec_list
     eng = GuardedEngine(arena, F, K, dec_list(params), precision=precision, max_frames=sum(counts), max_utts=len(counts),
                         z_dim=int(params["encoder.sample.mu.weight"].shape[0]))
     return eng.bind(counts, Rcap=Rcap, seeds=seeds)

@@ -1,9 +1,16 @@
-"""Shared helpers for the tests (fixture loading)."""
+"""Shared helpers for the tests (fixture loading, error measures, the GPU guard)."""
 import os
 
 import numpy as np
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def need_gpu():
+    import pytest
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
 
 
 def load_case(name):

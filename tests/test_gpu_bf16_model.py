@@ -39,7 +39,7 @@ import pytest
 import torch
 
 import bf16_model as bm
-from test_gpu_parity import need_gpu
+from helpers import need_gpu
 
 pytestmark = pytest.mark.gpu
 

@@ -4,7 +4,7 @@ Every power-of-two STFT gives F = n_fft/2 + 1 = 16k + 1 bins, and the kernels ar
 odd last bin out of the MFMA tiles (Fm = F - 1), the streaming kernels give a lane four consecutive bins.  Any other F --
 stft() takes any n_fft in [16, 4096], vaenmf_plan_create any F in 1..640 -- leaves a partly filled last bin tile, and
 often a partly filled last 4-bin chunk (Fm % 4 != 0).  One sweep over F runs every EM kernel against the numpy oracle
-from identical inputs; shape_class() restates the dispatch of plan.hip / chain.hip / stream.hip, a CPU test checks that
+from identical inputs; shape_class() (tests/dispatch_model.py) restates the dispatch of plan.hip / chain.hip / stream.hip, a CPU test checks that
 the sweep reaches every kernel form the dispatch has, and the GPU tests check that the library reports the kernels
 shape_class() predicts -- a later change of the dispatch makes the sweep fail instead of silently uncovering a kernel.
 
@@ -12,7 +12,6 @@ Tolerances are the ones tests/test_gpu_parity.py states for the same operations 
 test_m_step_and_chain_other_shapes, test_bench_mode_m_step_against_the_oracle, test_wave_chain_bf16_mode,
 test_stored_m_step_and_wiener_match_the_decoding_ones, test_fused_w_statistics_equal_the_two_kernel_path).
 """
-import os
 from types import SimpleNamespace
 
 import numpy as np
@@ -20,8 +19,10 @@ import pytest
 import torch
 
 import vaenmf_oracle as orc
-from helpers import GOLDEN, nrm_err, rel_err
-from test_gpu_parity import make_engine, need_gpu
+import em_support as es
+from dispatch_model import COUNTS, N_WAVE_TILES, shape_class
+from em_support import RecordingRNG, make_engine
+from helpers import GOLDEN, need_gpu, nrm_err, rel_err
 
 gpu = pytest.mark.gpu        # (per test, not per module: test_sweep_reaches_every_dispatch_class runs without a GPU)
 
@@ -56,97 +57,6 @@ RUN_F = [9, 201, 250, 273, 501, 514, 640]
 # bf16 (the bench mode)
 BF16_F = [9, 64, 81, 201, 221, 250, 251, 260, 272, 442, 501, 514, 528, 640]
 BF16_CASES = [(F, 8, 30) for F in BF16_F] + [(201, 10, 10), (514, 10, 10)]
-COUNTS = [21, 40, 9]
-N_WAVE_TILES = sum((n + 15) // 16 for n in COUNTS)
-# generator seed of a case's inputs when it is not 1000 + F (a case whose oracle margins leave out more than 15 % of the frames)
-SEEDS = {}
-
-
-def shape_class(F, K, precision, n_wave_tiles, R=30, n_cus=256):
-    """The dispatch of plan.hip (vaenmf_plan_create), chain.hip (vn_wchain_supported, vn_launch_wchain) and stream.hip
-    (launch_stream, launch_st, w_fused_ok, w_group_ok) with every switch at its default.  n_wave_tiles: 16-frame groups
-    of the batch; R: samples per frame of the stored M-step; n_cus: compute units of the device."""
-    bf16 = precision == "bf16"
-    Fs = (F + 15) // 16 * 16
-    Fm = F - 1 if (F % 16 == 1 and F > 16) else F            # plan.hip: the odd last bin leaves the tiles
-    Kp = 8 if K <= 8 else (16 if K <= 16 else 32)
-    team_tiles = (Fm + 15) // 16
-    geom = 3 if team_tiles == 16 else (0 if team_tiles <= 20 else (4 if team_tiles == 32 else 2))
-    tiles = (F + 15) // 16                                   # the wave chain keeps every bin on the MFMA path
-    if tiles > 17 and not (tiles == 33 and bf16):
-        chain_kernel, chain_form = 0, "team"
-    elif bf16 and tiles in (17, 33) and n_wave_tiles <= n_cus:
-        chain_kernel, chain_form = 2, "wchain4<%d>" % tiles
-    else:
-        chain_kernel = 1
-        chain_form = ("wchain<33,GT33>" if tiles == 33 else "wchain<17,exact>" if tiles == 17 else "wchain<5,exact>" if tiles == 5
-                      else "wchain<5>" if tiles < 5 else "wchain<17>")
-    nch = (Fm + 255) // 256
-    w_fused = 0
-    if bf16 and Kp == 8 and nch == 1 and R in (10, 30):
-        w_fused = 2 if n_wave_tiles <= n_cus else 1
-    return dict(Fs=Fs, Fm=Fm, Kp=Kp, chain_tiles=tiles, chain_kernel=chain_kernel, chain_form=chain_form,
-                partial_tile=F % 16 != 0, lo_in_lds=(not bf16) and tiles <= 5, pair_tiles=((tiles - 1) & ~1) if bf16 else 0,
-                team_tiles=team_tiles, geom=geom, nch=nch, tail=Fm % 4 != 0,
-                w_in_lds=Kp <= 8 or Fs * Kp * 4 <= 72 * 1024, w_fused=w_fused)
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-# The persistent loops, restated: which frames / wave tiles / tiles a wavefront or workgroup walks, trip by trip.  `cap` is
-# VAENMF_GRID_CAP (0: none).  tests/test_persistent_loops_cpu.py checks what the capped cases reach with these.
-def wave_tiles(counts):
-    """plan.hip, vaenmf_bind_batch_async: the 16-frame wave tiles of a batch, [(utterance, first frame, frames)]."""
-    off = np.concatenate([[0], np.cumsum(counts)])
-    return [(u, int(n), int(min(16, off[u + 1] - n))) for u in range(len(counts)) for n in range(off[u], off[u + 1], 16)]
-
-
-def decode_tiles(counts, geom):
-    """plan.hip: the tiles of decode_kernel, 64 frames with two teams (geometries 0 and 3), else 32."""
-    tf = 64 if geom in (0, 3) else 32
-    off = np.concatenate([[0], np.cumsum(counts)])
-    return [(u, int(n), int(min(tf, off[u + 1] - n))) for u in range(len(counts)) for n in range(off[u], off[u + 1], tf)]
-
-
-def stream_grid(NT, n_cus, cap=0, pipelined=False):
-    """stream.hip, launch_stream: workgroups (of four wavefronts) of the streaming kernels; pipelined: wstats_stream2_kernel."""
-    grid = min((2 if pipelined else 4) * n_cus, (NT + 3) // 4)
-    return cap if 0 < cap < grid else grid
-
-
-def wave_frames(NT, grid, wpb=4):
-    """stream.hip, wave_frames: (per, [(n_beg, n_end) per wavefront, workgroup-major]); n_beg >= n_end: no frames."""
-    nw = grid * wpb
-    per = (NT + nw - 1) // nw
-    return per, [(gw * per, min(gw * per + per, NT)) for gw in range(nw)]
-
-
-def chain_waves(precision, chain_tiles):
-    """chain.hip, vn_launch_wchain: wavefronts of a wchain_kernel workgroup."""
-    return 4 if (precision == "bf16x3" or chain_tiles == 33) else 8
-
-
-def chain_grid(n_wave_tiles, n_cus, cap=0):
-    """chain.hip, wc_launch_s."""
-    grid = min(n_wave_tiles, n_cus)
-    return cap if 0 < cap < grid else grid
-
-
-def chain_rounds(n_wave_tiles, grid, nwaves):
-    """chain.hip, wchain_kernel: {(workgroup, wavefront): [wave tile of round 0, 1, ..]}; tile (i nwaves + w) grid + b."""
-    rounds = (n_wave_tiles + grid * nwaves - 1) // (grid * nwaves)
-    return {(b, w): [wt for wt in ((i * nwaves + w) * grid + b for i in range(rounds)) if wt < n_wave_tiles]
-            for b in range(grid) for w in range(nwaves)}, rounds
-
-
-def decode_grid(n_tiles, n_cus, cap=0):
-    """engine.hip, launch_decode."""
-    grid = min(n_tiles, 2 * n_cus)
-    return cap if 0 < cap < grid else grid
-
-
-def decode_trips(n_tiles, grid):
-    """engine.hip, decode_kernel: [tiles of workgroup b, in the order of its trips]."""
-    return [list(range(b, n_tiles, grid)) for b in range(grid)]
 
 
 def test_sweep_reaches_every_dispatch_class():
@@ -194,113 +104,6 @@ def test_sweep_reaches_every_dispatch_class():
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-def _inputs(F, K, R, Dy=0, counts=None, seed=None):
-    """The recipe of test_m_step_and_chain_other_shapes: ragged batch, tilted spectrogram, Xavier decoder.  counts: the
-    frames per utterance (COUNTS); seed: the generator seed of the inputs (SEEDS, else 1000 + F)."""
-    params = orc.xavier_normal_params([F, 32, [128, 128]], seed=7, y_dim=Dy, bias_std=0.05)
-    g = np.random.default_rng(SEEDS.get((F, K, R), 1000 + F) if seed is None else seed)
-    counts = list(COUNTS if counts is None else counts)
-    NT = sum(counts)
-    c = SimpleNamespace(F=F, K=K, R=R, Dy=Dy, params=params, NT=NT, S_steps=6, ns=3, counts=counts)
-    c.Xs = [((g.standard_normal((n, F)) + 1j * g.standard_normal((n, F))) * (0.5 + 3 * np.exp(-np.arange(F) / 60.0))).astype(np.complex64) for n in counts]
-    c.W0 = [np.maximum(g.random((F, K)), 1e-8).astype(np.float32) for _ in counts]
-    c.H0 = [np.maximum(g.random((K, n)), 1e-8).astype(np.float32) for n in counts]
-    c.ys = [(g.random((n, Dy)) > 0.5).astype(np.float32) for n in counts] if Dy else [None] * len(counts)
-    c.Zs = (0.7 * g.standard_normal((NT, R, 32))).astype(np.float32)
-    c.gains = (0.5 + g.random(NT)).astype(np.float32)
-    c.eps = g.standard_normal((c.S_steps, NT, 32)).astype(np.float32)
-    c.uu = g.random((c.S_steps, NT)).astype(np.float32)
-    c.Z0 = (0.5 * g.standard_normal((NT, 32))).astype(np.float32)
-    c.off = np.concatenate([[0], np.cumsum(counts)])
-    return c
-
-
-def _engine(c, precision, Rcap=None, seeds=None):
-    eng = make_engine(c.params, c.F, c.K, c.counts, Rcap=Rcap or c.R, precision=precision, seeds=seeds)
-    eng.set_spectrogram(c.Xs)
-    eng.init_nmf(c.W0, c.H0)
-    if c.Dy:
-        eng.set_labels(torch.from_numpy(np.concatenate(c.ys)))
-    eng.g.copy_(torch.from_numpy(c.gains))
-    return eng
-
-
-def _query(eng, what):
-    from vaenmf import _lib
-    return _lib.lib().vaenmf_plan_query(eng._plan, getattr(_lib, what))
-
-
-def _n_cus():
-    return torch.cuda.get_device_properties(0).multi_processor_count
-
-
-def _oracle_at(c, eng, u, Zs=None):
-    """The oracle of utterance u in the engine's present state (W, H, g), with the variances of the samples Zs."""
-    sl = eng.utt_slice(u)
-    o = orc.MCEMOracle("M2" if c.Dy else "M1", 1)
-    o.init_parameters(c.Xs[u], c.params, c.K, 1e-8, orc.NumpyRNG(0), y=c.ys[u], W0=eng.W[u, :c.F, :c.K].cpu().numpy(),
-                      H0=eng.Ht[sl, :c.K].cpu().numpy().T.copy())
-    o.g = eng.g[sl].cpu().numpy().copy()
-    if Zs is not None:
-        o.compute_Vs(Zs[sl]); o.compute_Vs_scaled(); o.compute_Vx()
-    return o
-
-
-def _env(**kv):
-    class _E:
-        def __enter__(self):
-            for k, v in kv.items():
-                os.environ[k] = v
-
-        def __exit__(self, *a):
-            for k in kv:
-                os.environ.pop(k, None)
-    return _E()
-
-
-def _padding_is_zero(eng, *tensors):
-    F, K = eng.F, eng.K
-    assert float(eng.W[:, F:].abs().max() if eng.Fs > F else 0) == 0 and float(eng.W[:, :, K:].abs().max() if eng.Kp > K else 0) == 0
-    assert float(eng.Ht[:, K:].abs().max() if eng.Kp > K else 0) == 0
-    for t in tensors:
-        assert float(t[:, F:].abs().max() if eng.Fs > F else 0) == 0
-
-
-def _m_step_against(c, eng, oracles, R, cost, tu, tc, tag):
-    """W, H, g, cost of the engine after its M-step against the oracles' M_step() from the same state and samples."""
-    for name in ("W", "Ht", "g"):
-        assert bool(torch.isfinite(getattr(eng, name)).all()), (tag, name)
-    assert np.all(np.isfinite(cost)), tag
-    for u, o in enumerate(oracles):
-        o.M_step()
-        sl = eng.utt_slice(u)
-        e = (rel_err(eng.W[u, :c.F, :c.K].cpu().numpy(), o.W), rel_err(eng.Ht[sl, :c.K].cpu().numpy().T, o.H),
-             rel_err(eng.g[sl].cpu().numpy(), o.g), abs(cost[u] - o.compute_expected_neg_log_like()) / abs(cost[u]))
-        print("%s F=%d K=%d utt %d: W %.2e H %.2e g %.2e cost %.2e" % ((tag, c.F, c.K, u) + e))
-        assert e[0] < tu and e[1] < tu and e[2] < tu and e[3] < tc, (tag, u, e)
-    _padding_is_zero(eng)
-
-
-def _wiener_against(c, eng, oracles, out, tol, tag, absolute=False):
-    S, Nn, WFs, WFn = out
-    for t in (S, Nn, WFs, WFn):
-        assert bool(torch.isfinite(t).all()), tag
-    F = c.F
-    for u, o in enumerate(oracles):
-        ws, wn = o.compute_WF(sample=False)
-        sl = eng.utt_slice(u)
-        gs, gn = WFs[sl, :F].cpu().numpy().T, WFn[sl, :F].cpu().numpy().T
-        if absolute:      # bf16 mode: masks in [0, 1] to an absolute bound, the filtered spectrograms in L2
-            Sg = np.ascontiguousarray(S[sl, :F].cpu().numpy()).view(np.complex64)[..., 0].T
-            Ng = np.ascontiguousarray(Nn[sl, :F].cpu().numpy()).view(np.complex64)[..., 0].T
-            e = (float(np.max(np.abs(gs - ws))), float(np.max(np.abs(gn - wn))), nrm_err(Sg, ws * o.X), nrm_err(Ng, wn * o.X))
-        else:
-            e = (rel_err(gs, ws), rel_err(gn, wn))
-        print("%s F=%d K=%d utt %d: Wiener " % (tag, F, c.K, u) + " ".join("%.2e" % v for v in e))
-        assert max(e) < tol, (tag, u, e)
-    _padding_is_zero(eng, WFs, WFn, S.abs().sum(-1), Nn.abs().sum(-1))
-
-
 @gpu
 @pytest.mark.parametrize("F", [0, 641])
 def test_bin_counts_out_of_range_are_refused(F):
@@ -320,10 +123,10 @@ def test_split_mode_kernels_against_the_oracle(F, K, R):
     default kernel and with the team kernel, then the sample store: stored variances, streaming M-step and streaming
     Wiener filter against the oracle from the chain's own samples."""
     need_gpu()
-    c = _inputs(F, K, R)
-    sc = shape_class(F, K, "bf16x3", N_WAVE_TILES, R, _n_cus())
-    eng = _engine(c, "bf16x3")
-    assert eng.Fs == sc["Fs"] == _query(eng, "Q_FS") and eng.Kp == sc["Kp"]
+    c = es.inputs(F, K, R)
+    sc = shape_class(F, K, "bf16x3", N_WAVE_TILES, R, es.n_cus())
+    eng = es.engine(c, "bf16x3")
+    assert eng.Fs == sc["Fs"] == es.query(eng, "Q_FS") and eng.Kp == sc["Kp"]
     NT = c.NT
     eng.Zs.copy_(torch.from_numpy(c.Zs))
     # 1. decoder
@@ -334,16 +137,16 @@ def test_split_mode_kernels_against_the_oracle(F, K, R):
     assert e < 2e-4
     assert np.all(Vs[:, :, F:] == 0)
     # 2. Wiener filter from the given samples
-    oracles = [_oracle_at(c, eng, u, c.Zs) for u in range(len(COUNTS))]
-    _wiener_against(c, eng, oracles, eng.wiener(R, want_masks=True), 5e-4, "decoding")
+    oracles = [es.oracle_at(c, eng, u, c.Zs) for u in range(len(COUNTS))]
+    es.wiener_against(c, eng, oracles, eng.wiener(R, want_masks=True), 5e-4, "decoding")
     # 3. M-step and cost
     eng.m_step(R)
-    _m_step_against(c, eng, oracles, R, eng.cost_from_frames(R), 1e-3, 2e-4, "decoding M-step")
+    es.m_step_against(c, eng, oracles, R, eng.cost_from_frames(R), 1e-3, 2e-4, "decoding M-step")
     # 4. one replayed chain from this state: the oracle's trace first (it alone says which frames are comparable)
     refs = []
     for u in range(len(COUNTS)):
         sl = eng.utt_slice(u)
-        o = _oracle_at(c, eng, u)
+        o = es.oracle_at(c, eng, u)
         draws = []
         for m in range(c.S_steps):
             draws += [c.eps[m, sl].T.copy(), c.uu[m, sl].copy()]
@@ -358,12 +161,12 @@ def test_split_mode_kernels_against_the_oracle(F, K, R):
     assert left_out <= 0.15
     dev = eng.device
     for team in (False, True):
-        with _env(VAENMF_TEAM_CHAIN="1" if team else "0"):
+        with es.env(VAENMF_TEAM_CHAIN="1" if team else "0"):
             eng.Z.copy_(torch.from_numpy(c.Z0))
             eng.Zs.zero_()
             acc = eng.mh_chain(c.ns, c.S_steps - c.ns, 0.01, eps=torch.from_numpy(c.eps).to(dev), u=torch.from_numpy(c.uu).to(dev),
                                want_acc=True).cpu().numpy()
-            assert _query(eng, "Q_CHAIN_KERNEL") == (0 if team else sc["chain_kernel"])
+            assert es.query(eng, "Q_CHAIN_KERNEL") == (0 if team else sc["chain_kernel"])
         for sl, ref_acc, Zs_ref, keep in refs:
             ea = float(np.max(np.abs(acc[:, sl] - ref_acc)))
             ez = float(np.max(np.abs(eng.Zs[sl, :c.ns].cpu().numpy()[keep] - Zs_ref[keep]), initial=0.0))
@@ -374,18 +177,18 @@ def test_split_mode_kernels_against_the_oracle(F, K, R):
     eng.sample_store(True)
     for call, (ns, bi) in enumerate(((10, 4), (7, 0))):
         eng.mh_chain(ns, bi, 0.01, call=call)
-        assert _query(eng, "Q_CHAIN_KERNEL") == sc["chain_kernel"]
+        assert es.query(eng, "Q_CHAIN_KERNEL") == sc["chain_kernel"]
         Zc = eng.Zs[:, :ns].cpu().numpy().copy()
         got = eng.stored_variances(ns).cpu().numpy()
         ref = orc.decoder_forward(c.params, Zc.reshape(-1, 32)).reshape(NT, ns, F)
         e = rel_err(got[:, :, :F], ref)
         print("store F=%d (%d, %d): %.2e" % (F, ns, bi, e))
         assert np.all(np.isfinite(got)) and e < 2e-4
-        oracles = [_oracle_at(c, eng, u, Zc) for u in range(len(COUNTS))]
+        oracles = [es.oracle_at(c, eng, u, Zc) for u in range(len(COUNTS))]
         eng.m_step_stored()
-        assert _query(eng, "Q_W_FUSED") == sc["w_fused"] == 0
-        _m_step_against(c, eng, oracles, ns, eng.cost_from_frames(ns), 1e-3, 2e-4, "stored M-step (%d, %d)" % (ns, bi))
-        _wiener_against(c, eng, oracles, eng.wiener_stored(want_masks=True), 5e-4, "stored (%d, %d)" % (ns, bi))
+        assert es.query(eng, "Q_W_FUSED") == sc["w_fused"] == 0
+        es.m_step_against(c, eng, oracles, ns, eng.cost_from_frames(ns), 1e-3, 2e-4, "stored M-step (%d, %d)" % (ns, bi))
+        es.wiener_against(c, eng, oracles, eng.wiener_stored(want_masks=True), 5e-4, "stored (%d, %d)" % (ns, bi))
     eng.sample_store(False)
 
 
@@ -395,7 +198,7 @@ def test_fused_run_at_other_bin_counts(F):
     """BatchEngine.run() (the sample store on by default): finite, bit-identical to the same run stepped through mh_chain /
     m_step_stored / wiener_stored, and the middle utterance alone gives the bits it gives inside the batch."""
     need_gpu()
-    c = _inputs(F, 10, 12)
+    c = es.inputs(F, 10, 12)
     seeds = [5, 6, 7]
     niter, nsE, biE, nsW, biW = 3, 6, 5, 12, 7
 
@@ -408,7 +211,7 @@ def test_fused_run_at_other_bin_counts(F):
 
     eng = prep([0, 1, 2])
     cost, S, N = eng.run(niter, nsE, biE, nsW, biW, 0.01)
-    assert _query(eng, "Q_MSTEP_PATH") == 1
+    assert es.query(eng, "Q_MSTEP_PATH") == 1
     assert bool(torch.isfinite(cost).all()) and bool(torch.isfinite(S).all()) and bool(torch.isfinite(N).all())
     assert float(S.abs().max()) > 0 and float(S[:, F:].abs().max() if eng.Fs > F else 0) == 0
     eng2 = prep([0, 1, 2])
@@ -436,18 +239,18 @@ def test_bench_mode_kernels_against_the_oracle(F, K, R):
     stored M-step and Wiener filter against the oracle's from the chain's own samples, with every W-statistics kernel the
     shape has."""
     need_gpu()
-    c = _inputs(F, K, R)
-    sc = shape_class(F, K, "bf16", N_WAVE_TILES, R, _n_cus())
+    c = es.inputs(F, K, R)
+    sc = shape_class(F, K, "bf16", N_WAVE_TILES, R, es.n_cus())
     NT, nu = c.NT, len(COUNTS)
 
     def fresh():
-        eng = _engine(c, "bf16", seeds=[3, 4, 5])
+        eng = es.engine(c, "bf16", seeds=[3, 4, 5])
         eng.Z.copy_(torch.from_numpy(c.Z0))
         return eng
 
     # 7. decoder
     eng = fresh()
-    assert eng.Fs == sc["Fs"] == _query(eng, "Q_FS") and eng.Kp == sc["Kp"]
+    assert eng.Fs == sc["Fs"] == es.query(eng, "Q_FS") and eng.Kp == sc["Kp"]
     eng.Zs.copy_(torch.from_numpy(c.Zs))
     Vs = eng.decode(R).cpu().numpy()
     e = rel_err(Vs[:, :, :F], orc.decoder_forward(c.params, c.Zs.reshape(-1, 32)).reshape(NT, R, F))
@@ -455,11 +258,11 @@ def test_bench_mode_kernels_against_the_oracle(F, K, R):
     assert e < 5e-2 and np.all(Vs[:, :, F:] == 0)
 
     def chain(**env):
-        with _env(**env):
+        with es.env(**env):
             eng = fresh()
             acc = eng.mh_chain(c.ns, c.S_steps - c.ns, 0.01, eps=torch.from_numpy(c.eps).to(eng.device),
                                u=torch.from_numpy(c.uu).to(eng.device), want_acc=True).cpu().numpy()
-            return acc, eng.Zs[:, :c.ns].cpu().numpy().copy(), eng.Z.cpu().numpy().copy(), _query(eng, "Q_CHAIN_KERNEL")
+            return acc, eng.Zs[:, :c.ns].cpu().numpy().copy(), eng.Z.cpu().numpy().copy(), es.query(eng, "Q_CHAIN_KERNEL")
 
     dflt, team = chain(), chain(VAENMF_TEAM_CHAIN="1")
     assert dflt[3] == sc["chain_kernel"] and team[3] == 0
@@ -487,15 +290,15 @@ def test_bench_mode_kernels_against_the_oracle(F, K, R):
 
     # 8. / 9. the store: chain, streaming M-step, streaming Wiener filter
     def stored(**env):
-        with _env(**env):
+        with es.env(**env):
             eng = fresh()
             eng.sample_store(True)
             acc = eng.mh_chain(R, 4, 0.01, call=0, want_acc=True)
-            r = SimpleNamespace(eng=eng, chain_kernel=_query(eng, "Q_CHAIN_KERNEL"), acc=acc.cpu().numpy(), Z=eng.Z.cpu().numpy().copy(),
+            r = SimpleNamespace(eng=eng, chain_kernel=es.query(eng, "Q_CHAIN_KERNEL"), acc=acc.cpu().numpy(), Z=eng.Z.cpu().numpy().copy(),
                                 Zs=eng.Zs[:, :R].cpu().numpy().copy(), rows=eng.stored_variances(R).cpu().numpy())
-            r.oracles = [_oracle_at(c, eng, u, r.Zs) for u in range(nu)]
+            r.oracles = [es.oracle_at(c, eng, u, r.Zs) for u in range(nu)]
             r.cf = eng.m_step_stored().cpu().numpy().copy()
-            r.w_fused = _query(eng, "Q_W_FUSED")
+            r.w_fused = es.query(eng, "Q_W_FUSED")
             r.cost = eng.cost_from_frames(R)
             r.upd = [t.cpu().numpy().copy() for t in (eng.W, eng.Ht, eng.g)] + [r.cf]
             r.wf = eng.wiener_stored(want_masks=True)
@@ -504,8 +307,8 @@ def test_bench_mode_kernels_against_the_oracle(F, K, R):
     a = stored()
     assert a.chain_kernel == sc["chain_kernel"] and a.w_fused == sc["w_fused"]
     assert np.all(np.isfinite(a.rows)) and np.abs(a.Zs - c.Z0[:, None, :]).max() > 0.05
-    _m_step_against(c, a.eng, a.oracles, R, a.cost, 3e-2, 3e-3, "bench M-step")
-    _wiener_against(c, a.eng, a.oracles, a.wf, 1e-2, "bench stored", absolute=True)
+    es.m_step_against(c, a.eng, a.oracles, R, a.cost, 3e-2, 3e-3, "bench M-step")
+    es.wiener_against(c, a.eng, a.oracles, a.wf, 1e-2, "bench stored", absolute=True)
     names = ("W", "Ht", "g", "cost")
     if sc["w_fused"] == 2:
         b = stored(VAENMF_WGROUP="0")          # the tile kernel: bit for bit (test_group_w_statistics_equal_the_tile_kernel_bit_for_bit)
@@ -537,9 +340,9 @@ def test_stored_path_variants_against_the_oracle(F, variant):
     bias) and a fixed noise PSD (gains-only M-step, mcem.py:543-578), against the oracle from the chain's own samples."""
     need_gpu()
     K, R = (8, 10) if variant == "m2_labels" else (1, 10)
-    c = _inputs(F, K, R, Dy=1)
+    c = es.inputs(F, K, R, Dy=1)
     nu = len(COUNTS)
-    eng = _engine(c, "bf16", seeds=[3, 4, 5])
+    eng = es.engine(c, "bf16", seeds=[3, 4, 5])
     eng.Z.copy_(torch.from_numpy(c.Z0))
     Vb = None
     if variant == "nonmf_gains_only":
@@ -552,10 +355,10 @@ def test_stored_path_variants_against_the_oracle(F, variant):
     Zs = eng.Zs[:, :R].cpu().numpy().copy()
     assert np.abs(Zs - c.Z0[:, None, :]).max() > 0.05
     if variant == "m2_labels":
-        oracles = [_oracle_at(c, eng, u, Zs) for u in range(nu)]
+        oracles = [es.oracle_at(c, eng, u, Zs) for u in range(nu)]
         eng.m_step_stored()
-        _m_step_against(c, eng, oracles, R, eng.cost_from_frames(R), 3e-2, 3e-3, "M2 stored M-step")
-        _wiener_against(c, eng, oracles, eng.wiener_stored(want_masks=True), 1e-2, "M2 stored", absolute=True)
+        es.m_step_against(c, eng, oracles, R, eng.cost_from_frames(R), 3e-2, 3e-3, "M2 stored M-step")
+        es.wiener_against(c, eng, oracles, eng.wiener_stored(want_masks=True), 1e-2, "M2 stored", absolute=True)
         return
     oracles = []
     for u in range(nu):
@@ -573,23 +376,10 @@ def test_stored_path_variants_against_the_oracle(F, variant):
         print("noNMF F=%d utt %d: g %.2e cost %.2e" % (F, u, e[0], e[1]))
         assert e[0] < 3e-2 and e[1] < 3e-3
     out = eng.wiener_stored(want_masks=True)
-    _wiener_against(c, eng, oracles, out, 1e-2, "noNMF stored", absolute=True)
+    es.wiener_against(c, eng, oracles, out, 1e-2, "noNMF stored", absolute=True)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-class _Recorder:
-    def __init__(self, seed):
-        self.g, self.draws = orc.NumpyRNG(seed), []
-
-    def rand(self, *shape):
-        self.draws.append(self.g.rand(*shape))
-        return self.draws[-1]
-
-    def randn(self, *shape):
-        self.draws.append(self.g.randn(*shape))
-        return self.draws[-1]
-
-
 @gpu
 def test_reconstructor_at_25_ms():
     """wav -> stft (n_fft 400, F = 201) -> fused EM run in bench mode -> istft on three synthetic utterances."""
@@ -602,7 +392,7 @@ def test_reconstructor_at_25_ms():
     rec = Reconstructor(params, 201, 10, niter=3, fs=16000, wlen_sec=25e-3, precision="bf16", max_frames=1024, max_utts=4)
     wav = torch.from_numpy(np.concatenate(xs).astype(np.float32)).cuda()
     s_hat, n_hat, cost = rec.enhance(wav, lens)
-    assert _query(rec.eng, "Q_MSTEP_PATH") == 1
+    assert es.query(rec.eng, "Q_MSTEP_PATH") == 1
     assert s_hat.shape[0] == sum(lens) and n_hat.shape[0] == sum(lens) and cost.shape == (3, 3)
     assert torch.isfinite(s_hat).all() and torch.isfinite(n_hat).all() and torch.isfinite(cost).all()
     o = 0
@@ -622,7 +412,7 @@ def test_mcem_at_25_ms():
     F, K, niter = 201, 10, 3
     params = orc.xavier_normal_params([F, 32, [128, 128]], seed=3)
     Xo = orc.stft(x, fs=16000, wlen_sec=25e-3).T                       # (N, F)
-    rec = _Recorder(7)
+    rec = RecordingRNG(7)
     o = orc.MCEMOracle("M1", niter, 10, 10, 10, 10, 0.01)
     o.init_parameters(Xo, params, K, 1e-8, rec)                         # records the draws it takes
     c_ref = o.run()

@@ -24,9 +24,9 @@ import pytest
 import torch
 
 from contract_cases import BURNIN, BY_NAME, CASES, DECODE_CASES, DECODE_SAMPLES, NS, RCAP, VAR_RW, case_class, inputs, is_wide
+from em_support import make_engine, query
 from guarded import POISON, Arena, GuardError, bits, make_guarded_engine, power_spec, same_bits
-from test_gpu_parity import need_gpu
-from wide_cases import make_engine
+from helpers import need_gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -63,11 +63,6 @@ BUFFERS = {
     "S_hat": (lambda t, d: t[:, :d.F], (lambda t, d: t[:, d.F:],), ()), "N_hat": (lambda t, d: t[:, :d.F], (lambda t, d: t[:, d.F:],), ()),
     "WFs": (lambda t, d: t[:, :d.F], (lambda t, d: t[:, d.F:],), ()), "WFn": (lambda t, d: t[:, :d.F], (lambda t, d: t[:, d.F:],), ()),
 }
-
-
-def _query(eng, what):
-    from vaenmf import _lib
-    return _lib.lib().vaenmf_plan_query(eng._plan, getattr(_lib, what))
 
 
 class Pair:
@@ -184,7 +179,7 @@ def _prepare(P):
 
 def _chain_checks(P):
     for eng in P.engines:
-        assert _query(eng, "Q_CHAIN_KERNEL") == P.sc["chain_kernel"]        # (e)
+        assert query(eng, "Q_CHAIN_KERNEL") == P.sc["chain_kernel"]        # (e)
 
 
 def _m_step_skip(P):
@@ -228,7 +223,7 @@ def _sequence(P):
     P.step("vaenmf_m_step_stored", lambda eng, s: eng.m_step_stored(), skip=_m_step_skip(P))
     if not case.noise_psd:
         for eng in P.engines:
-            assert _query(eng, "Q_W_FUSED") == P.sc["w_fused"]
+            assert query(eng, "Q_W_FUSED") == P.sc["w_fused"]
     P.step("vaenmf_wiener_stored", lambda eng, s: dict(zip(("S_hat", "N_hat", "WFs", "WFn"), eng.wiener_stored(want_masks=True))))
     # 9. the Wiener phase's chain: device draws, Z only read, the samples not recorded where the kernel allows it
     no_zs = g.wide or (P.sc["chain_kernel"] != 0 and
@@ -259,8 +254,8 @@ def _sequence(P):
         P.step("vaenmf_em_run", run, skip=_m_step_skip(P))
         _chain_checks(P)
         for eng in P.engines:
-            assert _query(eng, "Q_EM_GRAPH") == graph and _query(eng, "Q_MSTEP_PATH") == 1
-            assert case.noise_psd or _query(eng, "Q_W_FUSED") == P.sc["w_fused"]
+            assert query(eng, "Q_EM_GRAPH") == graph and query(eng, "Q_MSTEP_PATH") == 1
+            assert case.noise_psd or query(eng, "Q_W_FUSED") == P.sc["w_fused"]
     assert bool(torch.isfinite(g._bS[:, :case.F]).all()) and float(g._bS.abs().max()) > 0
 
 
@@ -297,7 +292,7 @@ def test_large_batch_chain_and_stored_m_step(poison):
         _chain_checks(P)
         P.step("vaenmf_m_step_stored", lambda eng, s: eng.m_step_stored())
         for eng in P.engines:
-            assert _query(eng, "Q_W_FUSED") == P.sc["w_fused"]
+            assert query(eng, "Q_W_FUSED") == P.sc["w_fused"]
 
 
 @pytest.mark.parametrize("poison", sorted(POISON))

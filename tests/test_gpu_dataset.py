@@ -13,8 +13,7 @@ import torch
 
 import dataset_cases as dc
 from guarded import Arena, POISON
-from helpers import load_case
-from test_gpu_parity import need_gpu
+from helpers import load_case, need_gpu
 
 pytestmark = pytest.mark.gpu
 

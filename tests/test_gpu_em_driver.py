@@ -29,8 +29,8 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import vaenmf_oracle as orc
-from helpers import load_case
-from test_gpu_parity import dec_list, need_gpu
+from em_support import dec_list
+from helpers import load_case, need_gpu
 
 # sample capacity and (nsE, biE, nsWF, biWF) per shape: as small as the kernels allow.  The fused / per-group W statistics run
 # with exactly 10 or 30 samples per frame only (stream.hip: stream_form), so the bench-like shape takes 10

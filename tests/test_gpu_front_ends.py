@@ -26,16 +26,11 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import vaenmf_oracle as orc
-from helpers import GOLDEN
+from helpers import GOLDEN, need_gpu
 
 SENTINEL = -7.25
 POISON = (float("nan"), 1e30)
 OOB = "index -1 is out of bounds"
-
-
-def need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
 
 
 def _cuda(a):

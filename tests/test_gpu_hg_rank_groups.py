@@ -13,16 +13,16 @@ The shapes here are the ones where that can fail:
   counts      two utterances of 5 and 17 frames: a wavefront's block of frames crosses from one utterance's W to the next
 
 in both precisions (bf16 and float rows).  H, g and the cost are held to the float64 formulas of
-tests/test_gpu_rank_and_samples.py within that file's bounds (max(floor, 16 e32), from the float32 oracle's own error), are
+tests/test_gpu_rank_and_samples.py (in tests/em_support.py) within that file's bounds (max(floor, 16 e32), from the float32 oracle's own error), are
 the same bits in a second call from the same state, and the same bits for each utterance run alone with its seed.
 """
 import numpy as np
 import pytest
 import torch
 
-from test_gpu_bin_counts import _inputs, _oracle_at, _padding_is_zero, _query
-from test_gpu_parity import make_engine, need_gpu
-from test_gpu_rank_and_samples import _compare, _device_m_step, _reference
+import em_support as es
+from em_support import make_engine
+from helpers import need_gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -32,7 +32,7 @@ BURNIN = 3
 
 
 def _prep(c, precision, idx):
-    """The engine of the utterances idx of the case, in the state of _inputs, the store on."""
+    """The engine of the utterances idx of the case, in the state of es.inputs, the store on."""
     eng = make_engine(c.params, c.F, c.K, [COUNTS2[i] for i in idx], Rcap=c.R, precision=precision, seeds=[SEEDS2[i] for i in idx])
     eng.set_spectrogram([c.Xs[i] for i in idx])
     eng.init_nmf([c.W0[i] for i in idx], [c.H0[i] for i in idx])
@@ -54,24 +54,24 @@ def _m_step(eng, R):
 @pytest.mark.parametrize("F", [257, 65])
 def test_h_g_cost_over_rank_groups(F, K, R, precision):
     need_gpu()
-    c = _inputs(F, K, R, counts=COUNTS2)
+    c = es.inputs(F, K, R, counts=COUNTS2)
     tag = "%s F=%d K=%d R=%d" % (precision, F, K, R)
     eng = _prep(c, precision, [0, 1])
-    assert eng.Kp == (8 if K <= 8 else 16) == _query(eng, "Q_KP")
+    assert eng.Kp == (8 if K <= 8 else 16) == es.query(eng, "Q_KP")
     eng.mh_chain(R, BURNIN, 0.01, call=0)
     V = eng.stored_variances(R).cpu().numpy()
     assert np.all(np.isfinite(V)) and np.all(V[:, :, :F] > 0)
     # the float64 formulas from the state before the M-step and the rows the device stored
     refs = []
     for u in range(2):
-        o = _oracle_at(c, eng, u)
+        o = es.oracle_at(c, eng, u)
         o.Vs = np.ascontiguousarray(np.moveaxis(V[eng.utt_slice(u), :, :F], 0, -1))     # (R, F, N)
-        refs.append(_reference(o, "M1"))
+        refs.append(es.reference(o, "M1"))
     pre = [t.clone() for t in (eng.W, eng.Ht, eng.g)]
     first, cost = _m_step(eng, R)
     failures = []
-    _compare(tag, refs, lambda u: _device_m_step(c, eng, u, cost, "M1"), failures)
-    _padding_is_zero(eng)
+    es.compare(tag, refs, lambda u: es.device_m_step(c, eng, u, cost, "M1"), failures)
+    es.padding_is_zero(eng)
     # a second call from the same state: the same bits
     for t, p in zip((eng.W, eng.Ht, eng.g), pre):
         t.copy_(p)

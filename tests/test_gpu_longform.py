@@ -12,8 +12,7 @@ import pytest
 import torch
 
 from guarded import Arena, same_bits
-from helpers import load_case
-from test_gpu_parity import need_gpu
+from helpers import load_case, need_gpu
 
 pytestmark = pytest.mark.gpu
 

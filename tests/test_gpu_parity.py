@@ -24,27 +24,10 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import vaenmf_oracle as orc
-from helpers import load_case, rel_err, nrm_err, GOLDEN
-
-
-def need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-
-
-def dec_list(params):
-    if "decoder.hidden.1.weight" not in params:          # one hidden layer (h_dim = [128])
-        return [params["decoder.hidden.0.weight"], params["decoder.hidden.0.bias"], params["decoder.reconstruction.weight"], params["decoder.reconstruction.bias"]]
-    return [params["decoder.hidden.0.weight"], params["decoder.hidden.0.bias"], params["decoder.hidden.1.weight"],
-            params["decoder.hidden.1.bias"], params["decoder.reconstruction.weight"], params["decoder.reconstruction.bias"]]
-
-
-def make_engine(params, F, K, counts_N, Rcap, precision="bf16x3", seeds=None):
-    from vaenmf.engine import BatchEngine
-    z_dim = int(params["encoder.sample.mu.weight"].shape[0]) if "encoder.sample.mu.weight" in params else 32
-    eng = BatchEngine(F, K, dec_list(params), precision=precision, max_frames=sum(counts_N), max_utts=len(counts_N), z_dim=z_dim)
-    eng.bind(counts_N, Rcap=Rcap, seeds=seeds)
-    return eng
+import em_support as es
+from em_support import make_engine, replay_buffers, setup_from_case
+from helpers import load_case, need_gpu, rel_err, nrm_err, GOLDEN
+from stft_cases import check_stft_tr_dt
 
 
 @pytest.mark.parametrize("F,precision,tol", [(65, "bf16x3", 2e-4), (257, "bf16x3", 2e-4), (513, "bf16x3", 2e-4),
@@ -81,37 +64,6 @@ def test_decoder_forward_m2_label_bias():
     zin = np.concatenate([Zs, np.broadcast_to(y[:, None, :], (NT, R, Dy))], 2)
     ref = orc.decoder_forward(params, zin.reshape(NT * R, -1)).reshape(NT, R, F)
     assert rel_err(Vs[:, :, :F], ref) < 2e-4
-
-
-def setup_from_case(name, model, precision="bf16x3"):
-    z, params, draws, meta = load_case(name)
-    nsE, biE, nsW, biW = meta["counts"]
-    o = orc.MCEMOracle(model, meta["niter"], nsE, biE, nsW, biW, 0.01, reference_compat=True)
-    rng = orc.ReplayRNG(draws)
-    y = z["y"] if model == "M2" else None
-    o.init_parameters(z["X"], params, meta["K"], 1e-8, rng, y=y)
-    ns, bi = o.e_step_counts()
-    nw, bw = o.wf_counts()
-    eng = make_engine(params, meta["F"], meta["K"], [meta["N"]], Rcap=max(ns, nw), precision=precision)
-    eng.set_spectrogram([z["X"]])
-    eng.init_nmf([z["W0"]], [z["H0"]])
-    if y is not None:
-        eng.set_labels(torch.from_numpy(y))
-    eng.Z.zero_()
-    eng.Z[:, :meta["L"]].copy_(torch.from_numpy(np.ascontiguousarray(z["Z0"].T)))
-    return z, params, meta, o, rng, eng
-
-
-def replay_buffers(rng, S, N, L, dev):
-    """Take the next S (randn(L,N), rand(N)) pairs of the recorded stream (a 16-dimensional latent space: the recorded
-    draws fill columns 0..15 of the engine's 32-wide rows, the padding columns stay zero)."""
-    eps = np.zeros((S, N, 32), np.float32)
-    u = np.empty((S, N), np.float32)
-    for m in range(S):
-        eps[m, :, :rng.draws[rng.pos].shape[0]] = rng.draws[rng.pos].T
-        u[m] = rng.draws[rng.pos + 1]
-        rng.pos += 2
-    return torch.from_numpy(eps).to(dev), torch.from_numpy(u).to(dev)
 
 
 CASES = [("m1_f65", "M1"), ("m2_vad_f65", "M2"), ("m2_ibm_f65", "M2"), ("m1_f257", "M1"),
@@ -193,9 +145,8 @@ def test_full_run_replay(name, model):
     S, Nn, WFs, WFn = eng.wiener(nw, want_masks=True)
     assert rng.pos == len(rng.draws)
     assert np.max(np.abs(cost - z["cost"]) / np.abs(z["cost"])) < 2e-4
-    to_c = lambda t: np.ascontiguousarray(t[:, :F].cpu().numpy()).view(np.complex64).reshape(N, F).T
-    assert nrm_err(to_c(S), z["S_hat"]) < 2e-3
-    assert nrm_err(to_c(Nn), z["N_hat"]) < 2e-3
+    assert nrm_err(es.to_c(S, N, F), z["S_hat"]) < 2e-3
+    assert nrm_err(es.to_c(Nn, N, F), z["N_hat"]) < 2e-3
     assert rel_err(WFs[:, :F].cpu().numpy().T, z["WFs"]) < 5e-3
     assert np.max(np.abs(eng.Z[:, :meta["L"]].cpu().numpy().T - z["Z"])) < 1e-5
     assert rel_err(eng.W[0, :F, :meta["K"]].cpu().numpy(), z["W"]) < 2e-3
@@ -380,8 +331,7 @@ def test_stft_against_the_reference_train_and_validation_known_answers():
     tests/golden/stft_frames_tr_dt.npz): two utterances of each set, the bounds of the oracle's CPU test."""
     need_gpu()
     from vaenmf import stft as vstft
-    from test_oracle_golden import _check_stft_tr_dt
-    _check_stft_tr_dt(lambda x: vstft.stft(x, fs=16000, wlen_sec=64e-3, win="hann", hop_percent=0.25), 1e-5)
+    check_stft_tr_dt(lambda x: vstft.stft(x, fs=16000, wlen_sec=64e-3, win="hann", hop_percent=0.25), 1e-5)
 
 
 @pytest.mark.parametrize("F,K,R,model", [(513, 10, 30, "M1"), (513, 32, 10, "M2"), (257, 32, 30, "M1"), (129, 16, 40, "M1")])
@@ -1402,58 +1352,6 @@ def test_an_utterances_result_does_not_depend_on_its_batch(nfft, K, prec, store)
         assert np.array_equal(x, y)
 
 
-class _RecordingRNG:
-    """Seeded numpy generator (the oracle's NumpyRNG) that keeps what it drew, in order."""
-
-    def __init__(self, seed):
-        self.g, self.draws = orc.NumpyRNG(seed), []
-
-    def rand(self, *shape):
-        self.draws.append(self.g.rand(*shape))
-        return self.draws[-1]
-
-    def randn(self, *shape):
-        self.draws.append(self.g.randn(*shape))
-        return self.draws[-1]
-
-
-def _oracle_one_iteration(X, params, K, seed0, min_margin=5e-4):
-    """One EM iteration + the Wiener chain of the oracle on a recorded numpy stream; the stream's seed is advanced until every
-    accept / reject decision of both chains sits at least `min_margin` from its threshold (a replayed trajectory is only
-    comparable while the decisions agree; the reference-generated goldens were selected the same way, at 1e-3; the HIP
-    path's log-acceptances are within 1e-4 of the oracle's on these sizes)."""
-    for k in range(200):
-        o = orc.MCEMOracle("M1", 1, 10, 30, 25, 75, 0.01, reference_compat=True)
-        r = _RecordingRNG(seed0 + 1000 * k)
-        o.init_parameters(X, params, K, 1e-8, r)
-        out = dict(o=o, W0=o.W.copy(), H0=o.H.copy(), Z0=o.Z.copy())
-        ns, bi = o.e_step_counts()
-        nw, bw = o.wf_counts()
-        tr, p0 = [], len(r.draws)
-        Zs = o.sample_posterior(o.Z, ns, bi, trace=tr)
-        out["e_draws"], out["acc"], out["Zs"] = r.draws[p0:], np.stack([t["acc"] for t in tr]), Zs
-        o.Z = Zs[:, -1, :].T.copy()
-        o.compute_Vs(Zs); o.compute_Vs_scaled(); o.compute_Vx()
-        o.M_step()
-        out["W"], out["H"], out["g"], out["cost"] = o.W.copy(), o.H.copy(), o.g.copy(), float(o.compute_expected_neg_log_like())
-        tr2, p1 = [], len(r.draws)
-        Zw = o.sample_posterior(o.Z, nw, bw, trace=tr2)
-        out["w_draws"] = r.draws[p1:]
-        o.compute_Vs(Zw); o.compute_Vs_scaled(); o.compute_Vx()
-        out["WFs"], out["WFn"] = o.compute_WF(sample=False)
-        margins = [np.abs(np.log(d[2 * m + 1]) - t["acc"]).min() for d, trc in ((out["e_draws"], tr), (out["w_draws"], tr2)) for m, t in enumerate(trc)]
-        if min(margins) > min_margin:
-            return out
-    raise AssertionError("no stream with clear decisions found")
-
-
-def _replay_tensors(outs, key, S, dev):
-    # (ascontiguousarray: stacking transposed views keeps THEIR memory order, and the C ABI takes dense row-major buffers)
-    eps = np.ascontiguousarray(np.concatenate([np.stack([o[key][2 * m].T for m in range(S)]) for o in outs], 1))      # [S, NT, L]
-    u = np.ascontiguousarray(np.concatenate([np.stack([o[key][2 * m + 1] for m in range(S)]) for o in outs], 1))      # [S, NT]
-    return torch.from_numpy(eps).to(dev), torch.from_numpy(u).to(dev), u
-
-
 @pytest.mark.parametrize("counts,prec", [([1], "bf16x3"), ([3], "bf16x3"), ([17], "bf16x3"), ([1, 2, 19, 16, 1], "bf16x3"), ([1, 2, 19, 16, 1], "bf16")])
 def test_tiny_and_ragged_utterances_against_the_oracle(counts, prec):
     """Edge sizes: utterances of ONE frame, of fewer frames than a wavefront's 16, of 16 k + 1 and 16 k + 3 frames, alone and
@@ -1465,7 +1363,7 @@ def test_tiny_and_ragged_utterances_against_the_oracle(counts, prec):
     params = orc.xavier_normal_params([F, L, [128, 128]], seed=3, bias_std=0.05)
     gx = np.random.RandomState(11)
     Xs = [((gx.randn(n, F) + 1j * gx.randn(n, F)) * np.exp(0.5 * gx.randn(n, 1))).astype(np.complex64) for n in counts]
-    outs = [_oracle_one_iteration(X, params, K, 100 + i) for i, X in enumerate(Xs)]
+    outs = [es.oracle_iteration("M1", X, params, K, 100 + i, (10, 30, 25, 75), reference_compat=True, min_margin=5e-4) for i, X in enumerate(Xs)]
     ns, bi = outs[0]["o"].e_step_counts()
     nw, bw = outs[0]["o"].wf_counts()
     NT = sum(counts)
@@ -1476,7 +1374,7 @@ def test_tiny_and_ragged_utterances_against_the_oracle(counts, prec):
     eng.Z.zero_()
     eng.Z[:, :L].copy_(torch.from_numpy(np.ascontiguousarray(np.concatenate([o["Z0"].T for o in outs], 0))))
     S = ns + bi
-    eps, u_d, u = _replay_tensors(outs, "e_draws", S, dev)
+    eps, u_d, u = es.replay_tensors(outs, "e_draws", S, dev)
     acc_ref = np.concatenate([o["acc"] for o in outs], 1)
     acc = eng.mh_chain(ns, bi, 0.01, eps=eps, u=u_d, want_acc=True).cpu().numpy()
     assert acc.shape == (S, NT) and np.all(np.isfinite(acc))
@@ -1506,7 +1404,7 @@ def test_tiny_and_ragged_utterances_against_the_oracle(counts, prec):
         assert rel_err(eng.g[sl].cpu().numpy(), o["g"]) < 5e-4
         assert abs(cost[i] - o["cost"]) / abs(o["cost"]) < 1e-4
     # Wiener filter with the samples of a second chain
-    eps, u_d, _ = _replay_tensors(outs, "w_draws", nw + bw, dev)
+    eps, u_d, _ = es.replay_tensors(outs, "w_draws", nw + bw, dev)
     eng.mh_chain(nw, bw, 0.01, eps=eps, u=u_d, update_Z=False)
     Sh, Nh, WFs, WFn = eng.wiener(nw, want_masks=True)
     for i, o in enumerate(outs):

@@ -10,7 +10,7 @@ into a clipped last block and past wavefronts with nothing to do.  tests/test_pe
 assignments and checks that the cases below reach all that; this module runs them against the oracle.
 
 Tolerances are the ones tests/test_gpu_bin_counts.py and tests/test_gpu_rank_and_samples.py state for the same operation
-(the helpers are theirs): a capped launch does the same arithmetic per frame.  Beyond the oracle comparison the capped
+(the helpers are shared with them: tests/em_support.py): a capped launch does the same arithmetic per frame.  Beyond the oracle comparison the capped
 results are compared with the uncapped ones bit for bit wherever the value is computed per frame:
   * the chain: log-acceptances, Z, Zs and the store rows (a frame's chain reads nothing of another frame);
   * vaenmf_wiener_stored / vaenmf_wiener: S_hat, N_hat and the masks;
@@ -22,110 +22,28 @@ results are compared with the uncapped ones bit for bit wherever the value is co
 The last two tests use no switch: batches sized from the device's CU count reach a second frame per wavefront of the
 streaming kernels and a second round of wchain_kernel with the default grids.
 """
-import functools
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
-import vaenmf_oracle as orc
-from helpers import rel_err
-from test_gpu_bin_counts import (COUNTS, _engine, _env, _inputs, _m_step_against, _n_cus, _oracle_at, _query, _wiener_against,
-                                 chain_grid, chain_rounds, chain_waves, shape_class, stream_grid, wave_frames, wave_tiles)
-from test_gpu_parity import make_engine, need_gpu
-from test_gpu_rank_and_samples import (_case_inputs, _compare, _device_m_step, _device_wiener, _oracles_from, _padding_is_zero,
-                                       _prepare, _reference, _reset, decode_class, stream_class)
+import em_support as es
+from dispatch_model import (COUNTS, chain_form, chain_grid, chain_rounds, chain_waves, decode_class, default_chain_counts,
+                            default_stream_counts, shape_class, stream_class, stream_grid, wave_frames, wave_tiles)
+from em_support import make_engine
+from helpers import need_gpu, rel_err
+from persistent_cases import (CHAIN_CASES, MAX_LEFT_OUT, STREAM_CAPS, STREAM_CASES, TILE_CAPS, TILE_CASES, chain_inputs, chain_reference,
+                              replay_oracle)
 
-gpu = pytest.mark.gpu        # (per test: the case lists and _chain_reference are used by tests/test_persistent_loops_cpu.py)
+gpu = pytest.mark.gpu
 
 CAP = "VAENMF_GRID_CAP"
-# ---- the chain: a second ragged batch of 204 frames in 18 wave tiles, one workgroup
-CHAIN_COUNTS = [21, 40, 9, 1, 16, 33, 17, 3, 64]
-CHAIN_K, CHAIN_R, CHAIN_BURNIN = 10, 10, 4
-# (F, precision, labels): F = 9 / 64 wchain<5>, 80 <5,exact> (bf16x3: the lo fragments of W3 in LDS), 201 <17>, 257 <17,exact>,
-# 514 <33> (bf16 only; VAENMF_WCHAIN4=0 keeps the 17- and 33-tile bf16 shapes of this small batch on wchain_kernel); labels:
-# four wavefronts keep the layer-1 bias rows in registers (bf16x3), eight park them in LDS (bf16)
-CHAIN_CASES = [(9, "bf16x3", False), (80, "bf16x3", False), (201, "bf16x3", False), (257, "bf16x3", False), (201, "bf16x3", True),
-               (64, "bf16", False), (80, "bf16", False), (201, "bf16", False), (257, "bf16", False), (514, "bf16", False),
-               (257, "bf16", True)]
-CHAIN_FORMS = {"bf16x3": {"wchain<5>", "wchain<5,exact>", "wchain<17>", "wchain<17,exact>"},
-               "bf16": {"wchain<5>", "wchain<5,exact>", "wchain<17>", "wchain<17,exact>", "wchain<33,GT33>"}}
-# generator seed of a chain case's inputs when it is not 1000 + F: (F, labels) -> seed, chosen so that the ORACLE's decision
-# margins leave out at most 15 % of the frames (tests/test_persistent_loops_cpu.py asserts it; no device result enters)
-CHAIN_SEEDS = {}
-MAX_LEFT_OUT = 0.15
-
-# ---- the streaming kernels: the batch of the sweeps, one, two and four workgroups.  70 frames give 4 and 8 wavefronts blocks
-# of 18 and 9 frames, the last one clipped, none empty (4 * 18 = 8 * 9 = 72 < 70 + per); cap 4 (blocks of 5) leaves the last
-# two of 16 wavefronts without a frame and, at rank > 8, a workgroup that lies inside the utterance it staged.
-STREAM_CAPS = (1, 2, 4)
-# (F, K, R, variant, precision, switches)
-STREAM_CASES = [
-    (64, 4, 10, "M1", "bf16", {"VAENMF_WFUSED": "0"}),        # wstats_stream2 (bf16 rows), hg<RT 10>
-    (64, 4, 30, "M1", "bf16x3", {}),                          # float rows: wstats_stream at rank 8 through the batch loop, hg<RT 30>
-    (201, 8, 7, "M1", "bf16", {}),                            # TAIL; wstats_stream2, generic count
-    (201, 8, 30, "M1", "bf16", {"VAENMF_WFUSED": "0"}),       # wstats_stream2 with 30 of 32 rows
-    (201, 4, 7, "M1", "bf16x3", {}),                          # wstats_stream2 (float rows)
-    (201, 10, 30, "M1", "bf16", {}),                          # rank 16, one chunk of bf16 rows: two half batches of 16 (30 rows)
-    (251, 10, 10, "M1", "bf16x3", {}),                        # rank 16, W per workgroup; two half batches of 8 refilled a frame ahead
-    (257, 8, 10, "M2", "bf16", {"VAENMF_WFUSED": "0"}),       # labels; the extra bin (wx / nw refreshed per utterance)
-    (257, 8, 30, "noNMF", "bf16", {}),                        # fixed noise PSD: gains only
-    (442, 10, 30, "M1", "bf16", {}),                          # two chunks, TAIL, rank 16
-    (442, 32, 10, "M1", "bf16x3", {}),                        # two chunks, rank 32 in LDS
-    (514, 10, 10, "M1", "bf16", {}),                          # three chunks: two half batches of 5
-    (514, 32, 7, "M1", "bf16x3", {}),                         # three chunks, float rows (RB 5, HB 2), a partial last batch
-    (640, 4, 30, "M1", "bf16", {}),                           # three chunks at rank 8: the wave-private W restaged per utterance
-    (640, 32, 10, "M1", "bf16x3", {}),                        # W too large for LDS: every frame reads global memory
-]
-
-# ---- the tile loop of decode_kernel: (F, K, R, precision); caps 1 and 2
-TILE_CAPS = (1, 2)
-TILE_CASES = [(250, 8, 33, "bf16x3"), (250, 10, 10, "bf16"), (321, 8, 10, "bf16"), (321, 10, 33, "bf16x3"), (512, 8, 33, "bf16"),
-              (512, 32, 10, "bf16x3"), (640, 8, 10, "bf16x3"), (640, 32, 33, "bf16")]
-
-
-def chain_form(F, precision, n_wave_tiles):
-    """(kernel form with VAENMF_WCHAIN4=0 where the default is wchain4_kernel, whether that switch is needed)."""
-    sc = shape_class(F, CHAIN_K, precision, n_wave_tiles, CHAIN_R)
-    if sc["chain_kernel"] == 2:
-        return shape_class(F, CHAIN_K, precision, n_wave_tiles, CHAIN_R, n_cus=0)["chain_form"], True
-    return sc["chain_form"], False
-
-
-@functools.lru_cache(maxsize=None)
-def _chain_inputs(F, labels):
-    return _inputs(F, CHAIN_K, CHAIN_R, Dy=1 if labels else 0, counts=CHAIN_COUNTS, seed=CHAIN_SEEDS.get((F, labels)))
-
-
-def _replay_oracle(c, u):
-    """The oracle's chain of utterance u from the state of _inputs on the replayed draws: (log-acceptances [steps, n],
-    decisions, samples [n, ns, 32], frames whose every decision is at least 1e-2 from its threshold)."""
-    sl = slice(c.off[u], c.off[u + 1])
-    o = orc.MCEMOracle("M2" if c.Dy else "M1", 1)
-    o.init_parameters(c.Xs[u], c.params, c.K, 1e-8, orc.NumpyRNG(0), y=c.ys[u], W0=c.W0[u], H0=c.H0[u])
-    o.g = c.gains[sl].copy()
-    draws = []
-    for m in range(c.S_steps):
-        draws += [c.eps[m, sl].T.copy(), c.uu[m, sl].copy()]
-    o.rng = orc.ReplayRNG(draws)
-    tr = []
-    Zs_ref = o.sample_posterior(c.Z0[sl].T.copy(), c.ns, c.S_steps - c.ns, trace=tr)
-    acc = np.stack([t["acc"] for t in tr])
-    keep = np.abs(np.log(c.uu[:, sl]) - acc).min(0) > 1e-2
-    return SimpleNamespace(sl=sl, acc=acc, is_acc=np.stack([t["is_acc"] for t in tr]), Zs=Zs_ref, keep=keep)
-
-
-@functools.lru_cache(maxsize=None)
-def _chain_reference(F, labels):
-    """Computed once per (F, labels), shared by both precisions and the CPU test, left unchanged."""
-    c = _chain_inputs(F, labels)
-    refs = [_replay_oracle(c, u) for u in range(len(c.counts))]
-    return refs, 1.0 - float(np.concatenate([r.keep for r in refs]).mean())
+CHAIN_BURNIN = 4
 
 
 def _cap_env(cap, **env):
-    return _env(**dict(env, **({CAP: str(cap)} if cap else {})))
+    return es.env(**dict(env, **({CAP: str(cap)} if cap else {})))
 
 
 def _equal(a, b, names, tag):
@@ -145,28 +63,28 @@ def test_chain_rounds_against_the_oracle(F, precision, labels):
     test_bench_mode_kernels_against_the_oracle).  Device generator, store on: the store rows against the decoder of the
     chain's own samples.  Every array of both runs equals the uncapped launch's bit for bit."""
     need_gpu()
-    c = _chain_inputs(F, labels)
+    c = chain_inputs(F, labels)
     n_wt = len(wave_tiles(c.counts))
     form, need_switch = chain_form(F, precision, n_wt)
-    sc = shape_class(F, c.K, precision, n_wt, c.R, _n_cus())
+    sc = shape_class(F, c.K, precision, n_wt, c.R, es.n_cus())
     assert sc["chain_kernel"] == (2 if need_switch else 1)
     env = {"VAENMF_WCHAIN4": "0"} if need_switch else {}
     NT, R, dev = c.NT, c.R, "cuda:0"
 
     def run(cap):
         with _cap_env(cap, **env):
-            eng = _engine(c, precision, seeds=list(range(3, 3 + len(c.counts))))
-            assert _query(eng, "Q_WTILES") == n_wt
+            eng = es.engine(c, precision, seeds=list(range(3, 3 + len(c.counts))))
+            assert es.query(eng, "Q_WTILES") == n_wt
             eng.Z.copy_(torch.from_numpy(c.Z0))
             acc = eng.mh_chain(c.ns, c.S_steps - c.ns, 0.01, eps=torch.from_numpy(c.eps).to(dev), u=torch.from_numpy(c.uu).to(dev),
                                want_acc=True).cpu().numpy()
-            assert _query(eng, "Q_CHAIN_KERNEL") == 1
+            assert es.query(eng, "Q_CHAIN_KERNEL") == 1
             r = SimpleNamespace(eng=eng, acc=acc, Zs=eng.Zs[:, :c.ns].cpu().numpy().copy(), Z=eng.Z.cpu().numpy().copy())
             eng.Z.copy_(torch.from_numpy(c.Z0))
             eng.Zs.zero_()
             eng.sample_store(True)
             r.s_acc = eng.mh_chain(R, CHAIN_BURNIN, 0.01, call=0, want_acc=True).cpu().numpy()
-            assert _query(eng, "Q_CHAIN_KERNEL") == 1
+            assert es.query(eng, "Q_CHAIN_KERNEL") == 1
             r.s_Zs, r.s_Z = eng.Zs[:, :R].cpu().numpy().copy(), eng.Z.cpu().numpy().copy()
             r.rows = eng.stored_variances(R).cpu().numpy()
             return r
@@ -178,7 +96,7 @@ def test_chain_rounds_against_the_oracle(F, precision, labels):
     for a in arrays(capped):
         assert np.all(np.isfinite(a)), tag
     # 1. the oracle on the replayed draws
-    refs, left_out = _chain_reference(F, labels)
+    refs, left_out = chain_reference(F, labels)
     print("%s (%s): frames left out %.1f %%" % (tag, form, 100 * left_out))
     assert left_out <= MAX_LEFT_OUT
     for u, ref in enumerate(refs):
@@ -200,7 +118,7 @@ def test_chain_rounds_against_the_oracle(F, precision, labels):
     if precision == "bf16x3":
         for u in range(len(c.counts)):
             sl = capped.eng.utt_slice(u)
-            o = _oracle_at(c, capped.eng, u)
+            o = es.oracle_at(c, capped.eng, u)
             o.compute_Vs(capped.s_Zs[sl])
             e = rel_err(np.moveaxis(capped.rows[sl, :, :F], 0, -1), o.Vs)
             print("%s utt %d: store rows %.2e" % (tag, u, e))
@@ -228,15 +146,15 @@ def test_streaming_kernels_walk_several_frames(F, K, R, variant, precision, swit
     wavefront) against the float64 formulas fed the device's own stored rows, to the bounds of
     tests/test_gpu_rank_and_samples.py; every output equals the uncapped launch's bit for bit (module docstring)."""
     need_gpu()
-    c = _case_inputs(F, K, R, variant)
-    forms = stream_class(F, K, R, precision, variant, 6, _n_cus(), wfused=switches.get("VAENMF_WFUSED") != "0")
-    eng, Vb = _prepare(c, variant, precision, R)
+    c = es.case_inputs(F, K, R, variant)
+    forms = stream_class(F, K, R, precision, variant, 6, es.n_cus(), wfused=switches.get("VAENMF_WFUSED") != "0")
+    eng, Vb = es.prepare(c, variant, precision, R)
     eng.sample_store(True)
-    _reset(c, eng)
+    es.reset(c, eng)
     eng.mh_chain(R, 3, 0.01, call=0)
     V = eng.stored_variances(R).cpu().numpy()
     assert np.all(np.isfinite(V)) and np.all(V[:, :, :F] > 0)
-    refs = [_reference(o, variant) for o in _oracles_from(c, eng, variant, Vb, V[:, :, :F])]
+    refs = [es.reference(o, variant) for o in es.oracles_from(c, eng, variant, Vb, V[:, :, :F])]
     pre = [t.clone() for t in (eng.W, eng.Ht, eng.g)]
     failures = []
 
@@ -246,14 +164,14 @@ def test_streaming_kernels_walk_several_frames(F, K, R, variant, precision, swit
             for t, p in zip((eng.W, eng.Ht, eng.g), pre):
                 t.copy_(p)
             out = eng.wiener_stored(want_masks=True)
-            _compare(tag + " wiener", refs, lambda u: _device_wiener(c, eng, u, out), failures)
-            _padding_is_zero(eng, out[2], out[3], out[0].abs().sum(-1), out[1].abs().sum(-1))
+            es.compare(tag + " wiener", refs, lambda u: es.device_wiener(c, eng, u, out), failures)
+            es.padding_is_zero(eng, out[2], out[3], out[0].abs().sum(-1), out[1].abs().sum(-1))
             eng.m_step_stored()
             if variant != "noNMF":          # the two-kernel path: wstats_stream / wstats_stream2, not the fused or the group kernel
-                assert _query(eng, "Q_W_FUSED") == 0 and forms["wstats"]["kernel"] in ("wstats_stream", "wstats_stream2"), tag
+                assert es.query(eng, "Q_W_FUSED") == 0 and forms["wstats"]["kernel"] in ("wstats_stream", "wstats_stream2"), tag
         cost = eng.cost_from_frames(R)
-        _compare(tag + " m-step", refs, lambda u: _device_m_step(c, eng, u, cost, variant), failures)
-        _padding_is_zero(eng)
+        es.compare(tag + " m-step", refs, lambda u: es.device_m_step(c, eng, u, cost, variant), failures)
+        es.padding_is_zero(eng)
         return [t.clone() for t in out] + [t.clone() for t in (eng.W, eng.Ht, eng.g, eng.cost_frames)]
 
     names = ("S_hat", "N_hat", "WFs", "WFn", "W", "Ht", "g", "cost_frames")
@@ -273,10 +191,10 @@ def test_tile_loop_walks_several_tiles(F, K, R, precision):
     test_decoding_kernels_against_the_oracle_from_the_decoded_variances; every output equals the uncapped launch's bit
     for bit."""
     need_gpu()
-    c = _case_inputs(F, K, R, "M1")
+    c = es.case_inputs(F, K, R, "M1")
     dc = decode_class(F, K, R, precision)
-    eng, _ = _prepare(c, "M1", precision, R)
-    assert _query(eng, "Q_TILES") == sum((n + (63 if dc["geom"] in (0, 3) else 31)) // (64 if dc["geom"] in (0, 3) else 32) for n in COUNTS)
+    eng, _ = es.prepare(c, "M1", precision, R)
+    assert es.query(eng, "Q_TILES") == sum((n + (63 if dc["geom"] in (0, 3) else 31)) // (64 if dc["geom"] in (0, 3) else 32) for n in COUNTS)
     eng.Zs.copy_(torch.from_numpy(c.Zs))
     pre = [t.clone() for t in (eng.W, eng.Ht, eng.g)]
     failures, refs = [], []
@@ -290,7 +208,7 @@ def test_tile_loop_walks_several_tiles(F, K, R, precision):
             Vn = V.cpu().numpy()
             assert np.all(np.isfinite(Vn)) and np.all(Vn[:, :, F:] == 0)
             if not refs:                    # (once: the capped runs must reproduce these variances bit for bit, checked below)
-                oracles = _oracles_from(c, eng, "M1", None, Vn[:, :, :F])
+                oracles = es.oracles_from(c, eng, "M1", None, Vn[:, :, :F])
                 for u, o in enumerate(oracles):
                     mine = o.Vs
                     o.compute_Vs(c.Zs[eng.utt_slice(u)])
@@ -298,14 +216,14 @@ def test_tile_loop_walks_several_tiles(F, K, R, precision):
                     print("%s utt %d: decode %.2e" % (tag, u, e))
                     assert e < (2e-4 if precision == "bf16x3" else 5e-2), (tag, u, e)
                     o.Vs = mine
-                refs.extend(_reference(o, "M1") for o in oracles)
+                refs.extend(es.reference(o, "M1") for o in oracles)
             out = eng.wiener(R, want_masks=True)
-            _compare(tag + " wiener", refs, lambda u: _device_wiener(c, eng, u, out), failures)
-            _padding_is_zero(eng, out[2], out[3], out[0].abs().sum(-1), out[1].abs().sum(-1))
+            es.compare(tag + " wiener", refs, lambda u: es.device_wiener(c, eng, u, out), failures)
+            es.padding_is_zero(eng, out[2], out[3], out[0].abs().sum(-1), out[1].abs().sum(-1))
             eng.m_step(R)
         cost = eng.cost_from_frames(R)
-        _compare(tag + " m-step", refs, lambda u: _device_m_step(c, eng, u, cost, "M1"), failures)
-        _padding_is_zero(eng)
+        es.compare(tag + " m-step", refs, lambda u: es.device_m_step(c, eng, u, cost, "M1"), failures)
+        es.padding_is_zero(eng)
         return [V] + [t.clone() for t in out] + [t.clone() for t in (eng.W, eng.Ht, eng.g, eng.cost_frames)]
 
     names = ("decode", "S_hat", "N_hat", "WFs", "WFn", "W", "Ht", "g", "cost_frames")
@@ -323,7 +241,7 @@ def test_em_run_graph_is_keyed_on_the_grid_cap():
     and uncapped once more, which replays the first graph.  Every capped run gives the results of the capped run stepped
     through mh_chain / m_step_stored / wiener_stored."""
     need_gpu()
-    c = _inputs(65, 10, 10)
+    c = es.inputs(65, 10, 10)
     niter, nsE, biE, nsW, biW = 2, 8, 3, 10, 4
     seeds = [5, 6, 7]
 
@@ -335,15 +253,15 @@ def test_em_run_graph_is_keyed_on_the_grid_cap():
     def fused(eng):
         load(eng)
         cost, S, N = eng.run(niter, nsE, biE, nsW, biW, 0.01)
-        assert _query(eng, "Q_MSTEP_PATH") == 1
+        assert es.query(eng, "Q_MSTEP_PATH") == 1
         return SimpleNamespace(cost=cost.cpu().numpy(), out=[S, N, eng.W.clone(), eng.Ht.clone(), eng.g.clone(), eng.Z.clone()],
-                               graph=_query(eng, "Q_EM_GRAPH"))
+                               graph=es.query(eng, "Q_EM_GRAPH"))
 
-    eng = _engine(c, "bf16", seeds=seeds)
+    eng = es.engine(c, "bf16", seeds=seeds)
     plain = [fused(eng) for _ in range(3)]
     with _cap_env(1):
         capped = [fused(eng) for _ in range(3)]
-        ref = _engine(c, "bf16", seeds=seeds)
+        ref = es.engine(c, "bf16", seeds=seeds)
         load(ref)
         ref.sample_store(True)
         cost = np.zeros((len(COUNTS), niter))
@@ -365,47 +283,32 @@ def test_em_run_graph_is_keyed_on_the_grid_cap():
         assert np.array_equal(r.cost, plain[0].cost)
 
 
-# ---------------------------------------------------------------------------------------------------------------------
-# the default launch: no switch, sizes from the device's CU count
-def default_stream_counts(n_cus, n_utt=40):
-    """About n_utt ragged utterances with 16 n_cus + 41 frames in all: two frames per wavefront of the 4 n_cus workgroups, the
-    last block clipped to one frame, the wavefronts behind it empty."""
-    NT = 16 * n_cus + 41
-    cuts = np.sort(np.random.default_rng(40).choice(np.arange(1, NT), n_utt - 1, replace=False))
-    return [int(v) for v in np.diff(np.concatenate([[0], cuts, [NT]]))]
-
-
-def default_chain_counts(n_cus):
-    """8 n_cus + 52 utterances of 1..16 frames, one wave tile each: a second round of wchain_kernel's eight wavefronts."""
-    return [1 + (7 * u) % 16 for u in range(8 * n_cus + 52)]
-
-
 @gpu
 def test_default_streaming_launch_reaches_a_second_frame():
     """F = 65, K = 4, R = 10, bf16: the stored M-step, its cost and the stored Wiener filter of a batch of 16 n_cus + 41 frames
     against the oracle per utterance (the bounds of test_bench_mode_kernels_against_the_oracle), with the default W-statistics
     kernel and on the two-kernel path (wstats_stream2: 2 n_cus workgroups, three frames per wavefront)."""
     need_gpu()
-    n = _n_cus()
+    n = es.n_cus()
     counts = default_stream_counts(n)
     NT, F, K, R = sum(counts), 65, 4, 10
     per, blocks = wave_frames(NT, stream_grid(NT, n))
     per2, _ = wave_frames(NT, stream_grid(NT, n, pipelined=True))
     assert per >= 2 and per2 >= 2 and any(0 < e - b < per for b, e in blocks) and any(b >= e for b, e in blocks)
-    c = _inputs(F, K, R, counts=counts)
+    c = es.inputs(F, K, R, counts=counts)
     for switches in ({}, {"VAENMF_WFUSED": "0"}):
-        eng = _engine(c, "bf16", seeds=list(range(3, 3 + len(counts))))
+        eng = es.engine(c, "bf16", seeds=list(range(3, 3 + len(counts))))
         eng.Z.copy_(torch.from_numpy(c.Z0))
         eng.sample_store(True)
         eng.mh_chain(R, 4, 0.01, call=0)
         Zs = eng.Zs[:, :R].cpu().numpy().copy()
-        oracles = [_oracle_at(c, eng, u, Zs) for u in range(len(counts))]
-        with _env(**switches):
+        oracles = [es.oracle_at(c, eng, u, Zs) for u in range(len(counts))]
+        with es.env(**switches):
             eng.m_step_stored()
-            assert (_query(eng, "Q_W_FUSED") == 0) == bool(switches)
+            assert (es.query(eng, "Q_W_FUSED") == 0) == bool(switches)
         tag = "default grid, %s" % ("two kernels" if switches else "fused W statistics")
-        _m_step_against(c, eng, oracles, R, eng.cost_from_frames(R), 3e-2, 3e-3, tag)
-        _wiener_against(c, eng, oracles, eng.wiener_stored(want_masks=True), 1e-2, tag, absolute=True)
+        es.m_step_against(c, eng, oracles, R, eng.cost_from_frames(R), 3e-2, 3e-3, tag)
+        es.wiener_against(c, eng, oracles, eng.wiener_stored(want_masks=True), 1e-2, tag, absolute=True)
         eng.close()
 
 
@@ -415,13 +318,13 @@ def test_default_chain_launch_reaches_a_second_round():
     the first and in the second (last) round of a wavefront, each run alone with its seed: Z, Zs and the store rows are
     bit equal (the batch independence of the device generator's chains).  Two more against the oracle on replayed draws."""
     need_gpu()
-    n = _n_cus()
+    n = es.n_cus()
     counts = default_chain_counts(n)
     U, F, K, R, bi = len(counts), 65, 8, 4, 2
-    c = _inputs(F, K, R, counts=counts)
+    c = es.inputs(F, K, R, counts=counts)
     seeds = [100 + u for u in range(U)]
-    eng = _engine(c, "bf16", seeds=seeds)
-    assert _query(eng, "Q_WTILES") == U > 8 * n
+    eng = es.engine(c, "bf16", seeds=seeds)
+    assert es.query(eng, "Q_WTILES") == U > 8 * n
     where, rounds = chain_rounds(U, chain_grid(U, n), chain_waves("bf16", 5))
     assert rounds >= 2
     round_of = {wt: i for tiles in where.values() for i, wt in enumerate(tiles)}
@@ -433,7 +336,7 @@ def test_default_chain_launch_reaches_a_second_round():
     eng.Z.copy_(torch.from_numpy(c.Z0))
     eng.sample_store(True)
     eng.mh_chain(R, bi, 0.01, call=0)
-    assert _query(eng, "Q_CHAIN_KERNEL") == 1
+    assert es.query(eng, "Q_CHAIN_KERNEL") == 1
     Z, Zs, rows = eng.Z.clone(), eng.Zs[:, :R].clone(), eng.stored_variances(R)
     assert bool(torch.isfinite(rows).all()) and float((Zs - eng.Z.new_tensor(c.Z0)[:, None, :]).abs().max()) > 0.05
     one = make_engine(c.params, F, K, [16], Rcap=R, precision="bf16")       # one engine, bound again per utterance
@@ -446,7 +349,7 @@ def test_default_chain_launch_reaches_a_second_round():
         one.Z.copy_(torch.from_numpy(c.Z0[sl]))
         one.sample_store(True)
         one.mh_chain(R, bi, 0.01, call=0)
-        assert _query(one, "Q_CHAIN_KERNEL") == 1
+        assert es.query(one, "Q_CHAIN_KERNEL") == 1
         _equal((one.Z, one.Zs[:, :R], one.stored_variances(R)), (Z[sl], Zs[sl], rows[sl]), ("Z", "Zs", "store rows"),
                "utterance %d (round %d) alone" % (u, round_of[u]))
     one.close()
@@ -459,7 +362,7 @@ def test_default_chain_launch_reaches_a_second_round():
                        want_acc=True).cpu().numpy()
     assert np.all(np.isfinite(acc))
     for u in (first[len(first) // 3], last[len(last) // 3]):
-        ref = _replay_oracle(c, u)
+        ref = replay_oracle(c, u)
         e = float(np.max(np.abs(acc[0, ref.sl] - ref.acc[0])))
         print("default grid, utterance %d (round %d, %d frames): first-step acc %.3f" % (u, round_of[u], counts[u], e))
         assert e < 0.5

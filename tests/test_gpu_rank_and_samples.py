@@ -3,14 +3,14 @@
 tests/test_gpu_bin_counts.py sweeps the bin count F.  The other two sizes that pick a kernel are the rank (1..32, padded
 to KP = 8 / 16 / 32) and the number of posterior samples per frame, which no entry point limits: the streaming kernels of
 stream.hip read a frame's stored rows in register batches of RowBatch::RB rows (and wstats_stream in halves of HB), the
-decoding kernels of engine.hip in chunks of 32 samples.  stream_class() and decode_class() restate that dispatch, a CPU
+decoding kernels of engine.hip in chunks of 32 samples.  stream_class() and decode_class() (tests/dispatch_model.py) restate that dispatch, a CPU
 test checks that the case lists below reach every form of it, and the GPU tests check the plan queries against it.
 
 The reference.  The oracle is given the variances the device itself produced -- eng.stored_variances(R) for the store,
 eng.decode(R) for the decoding path -- so that only the arithmetic of the M-step / Wiener kernels separates the two, in
 both precisions: the kernels' own arithmetic is fp32 on the stored rows.  The modes of decode_kernel share one decode
 routine (decode_tiles, the odd last bin's nyq_logit included), so mode STORE writes the very variances the other modes
-use.  The reference proper is a float64 evaluation of the same formulas (m_step64, gains_step64, wiener64: mcem.py:90-152,
+use.  The reference proper is a float64 evaluation of the same formulas (m_step64, gains_step64, wiener64 in tests/em_support.py: mcem.py:90-152,
 :543-578, :486-488, :70 without any intermediate cast); with e32 the error of the float32 oracle against it, a device
 result must lie within
 
@@ -26,7 +26,7 @@ batch edge of the case, in the float64 evaluation, and asserts that the bound is
 that causes in g and in the masks -- so a kernel that reads a wrong row, skips one or counts one twice cannot pass.
 
 The samples.  The stored path runs the chain with the device generator; a rejected step repeats a sample, so there two
-neighbouring rows can be equal and the wrong-row figures, computed from the independent draws of _inputs, stand in for
+neighbouring rows can be equal and the wrong-row figures, computed from the independent draws of es.inputs, stand in for
 the chain's.  The decoding path is given those very draws.  What the sweep found is such a row: wstats_stream_kernel
 dropped the fifth of five float rows in three 256-bin chunks (RB = 5, two half batches of 2), W off by 1e-2.
 
@@ -48,73 +48,14 @@ import pytest
 import torch
 
 import vaenmf_oracle as orc
-from helpers import nrm_err, rel_err
-from test_gpu_bin_counts import (COUNTS, N_WAVE_TILES, _engine, _env, _inputs, _n_cus, _oracle_at, _padding_is_zero, _query,
-                                 shape_class)
-from test_gpu_parity import need_gpu
+import em_support as es
+from dispatch_model import COUNTS, N_WAVE_TILES, decode_class, shape_class, stream_class
+from helpers import need_gpu, rel_err
 
 gpu = pytest.mark.gpu        # (per test: the three tests on the restatement, the float64 formulas and the bound run without a GPU)
 
 PRECISIONS = ["bf16x3", "bf16"]
-FLOOR = dict(W=2e-5, H=2e-5, g=2e-5, mask=2e-5, S_hat=2e-5, N_hat=2e-5, cost=1e-6)
-E32_FACTOR = 16
 BURNINS = lambda R: (0, 3, R + 5)          # none, short (shorter than R from R = 5 up), longer than R: the slot map of R + 1 slots
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-# the dispatch, restated
-def _row_class(R, RB, HB=0):
-    """Which of a kernel's row loops a frame of R rows takes: within the first half batch, within one batch, several
-    full batches, or a partial last batch."""
-    if HB and R <= HB:
-        return "half"
-    if R <= (2 * HB if HB else RB):      # (wstats_stream: two half batches; an odd RB = 2 HB + 1 rows go through the batch loop)
-        return "one"
-    return "exact" if R % RB == 0 else "partial"
-
-
-def stream_class(F, K, R, precision, variant, n_wave_tiles, n_cus=256, wfused=True, wgroup=True):
-    """stream.hip: launch_stream / launch_kp / launch_one / launch_st, w_fused_ok, w_group_ok and the RowBatch sizes of
-    wstats_stream_kernel, wstats_stream2_kernel, hg_stream_kernel and wf_stream_kernel.  variant: "M1", "M2" (labels) or
-    "noNMF" (fixed noise PSD: gains only).  wfused / wgroup: the switches VAENMF_WFUSED / VAENMF_WGROUP.
-    Returns {"wstats": .., "hg": .., "wf": ..}; "wstats" is None when only the gains move."""
-    bf16 = precision == "bf16"
-    store = "bf16" if bf16 else "float"
-    Fs = (F + 15) // 16 * 16
-    Fm = F - 1 if (F % 16 == 1 and F > 16) else F
-    KP = 8 if K <= 8 else (16 if K <= 16 else 32)
-    NCH = min((Fm + 255) // 256, 3)
-    tail = Fm % 4 != 0
-    base = (32 if bf16 else 16) // NCH                                    # RowBatch<NCH, ST>::RB
-    common = dict(NCH=NCH, KP=KP, store=store, tail=tail, extra_bin=F != Fm, w_in_lds=KP <= 8 or Fs * KP * 4 <= 72 * 1024)
-
-    def kind(name, RB, HB=0, TAIL=False, RT=0, **kw):
-        return dict(common, kernel=name, RB=RB, HB=HB, TAIL=TAIL, RT=RT, rows=_row_class(R, RB, HB), **kw)
-
-    gains_only = variant == "noNMF"
-    if gains_only:
-        ws = None
-    elif bf16 and KP == 8 and NCH == 1 and R in (10, 30) and wfused:      # w_fused_ok; w_group_ok: a small batch
-        ws = kind("wstats_group" if (n_wave_tiles <= n_cus and wgroup) else "wstats_fused", 32, RT=R)
-    elif NCH == 1 and KP <= 8 and R <= base:
-        ws = kind("wstats_stream2", base)
-    else:
-        ws = kind("wstats_stream", base, HB=base // 2)
-    RT = 0
-    if (NCH == 1 and KP <= 8 and R in (10, 30)) or (NCH == 2 and bf16 and KP == 16 and R == 30):
-        RT = R                                                             # the exact-count forms (not with TAIL)
-    RBhg = 32 if ((bf16 and NCH == 2 and KP <= 16) or (not bf16 and NCH == 1 and KP <= 8)) else base
-    hg = kind("hg_stream", RBhg, TAIL=tail, RT=0 if tail else RT, rt_shape=RT, gains_only=gains_only)
-    wf = kind("wf_stream", base, TAIL=tail)
-    return dict(wstats=ws, hg=hg, wf=wf)
-
-
-def decode_class(F, K, R, precision):
-    """engine.hip: launch_decode (with_geom, then the rank) and decode_kernel's loop over chunks of 32 samples."""
-    sc = shape_class(F, K, precision, N_WAVE_TILES)
-    m = R % 32
-    return dict(geom=sc["geom"], split=precision == "bf16x3", KP=sc["Kp"], chunks=(R + 31) // 32,
-                rmod="0" if m == 0 else ("1..15" if m < 16 else ("16" if m == 16 else "17..31")), extra_bin=F != sc["Fm"])
 
 
 def _stored_runs(F, K, R, variant, precision, n_cus=256):
@@ -290,108 +231,11 @@ def test_sweep_reaches_every_kernel_form_over_rank_and_samples():
     assert len(PRECISIONS) * (len(STORED_CASES) + len(DECODE_CASES)) <= 250
 
 
-# ---------------------------------------------------------------------------------------------------------------------
-# the float64 formulas
-def m_step64(X2, Vs, W, H, g):
-    """mcem.py:90-152 and :70 in float64.  X2 (F, N), Vs (R, F, N), W (F, K), H (K, N), g (N,)."""
-    iv = 1.0 / (g * Vs + W @ H)
-    W = W * np.sqrt(((X2 * np.sum(iv * iv, 0)) @ H.T) / (np.sum(iv, 0) @ H.T))          # :107-110
-    iv = 1.0 / (g * Vs + W @ H)                                                          # :113-114
-    H = H * np.sqrt((W.T @ (X2 * np.sum(iv * iv, 0))) / (W.T @ np.sum(iv, 0)))          # :118-121
-    Vb = W @ H                                                                           # :124-125
-    nrm = np.sum(np.abs(W), 0)                                                           # :129-133
-    W, H = W / nrm[None, :], H * nrm[:, None]
-    g, cost = gains_step64(X2, Vs, Vb, g)
-    return W, H, g, cost
-
-
-def gains_step64(X2, Vs, Vb, g):
-    """mcem.py:138-152 (= :564-578) and :70 in float64."""
-    iv = 1.0 / (g * Vs + Vb)
-    g = g * np.sqrt(np.sum(X2 * np.sum(Vs * iv * iv, 0), 0) / np.sum(np.sum(Vs * iv, 0), 0))
-    Vx = g * Vs + Vb
-    return g, float(np.mean(np.log(Vx) + X2 / Vx))
-
-
-def wiener64(Vs, Vb, g):
-    """mcem.py:486-488 in float64."""
-    Vx = g * Vs + Vb
-    return np.mean(g * Vs / Vx, 0), np.mean(Vb / Vx, 0)
-
-
-def _reference(o, variant, Vs64=None):
-    """From an oracle that holds the state before the M-step and the samples' variances o.Vs: the float64 results
-    (of Vs64 instead of o.Vs where given), and the float32 oracle's own (which runs its M-step)."""
-    f8 = lambda a: np.asarray(a, np.float64)
-    X2, Vs, g, X = f8(o.X_abs_2), (f8(o.Vs) if Vs64 is None else Vs64), f8(o.g), o.X.astype(np.complex128)
-    if variant == "noNMF":
-        Vb = f8(o.Vb)
-        g2, cost = gains_step64(X2, Vs, Vb, g)
-        ref = dict(g=g2, cost=cost)
-    else:
-        Vb = f8(o.W) @ f8(o.H)
-        W2, H2, g2, cost = m_step64(X2, Vs, f8(o.W), f8(o.H), g)
-        ref = dict(W=W2, H=H2, g=g2, cost=cost)
-    ws, wn = wiener64(Vs, Vb, g)
-    ref.update(mask=np.stack([ws, wn]), S_hat=ws * X, N_hat=wn * X)
-    if Vs64 is not None:
-        return ref, None
-    o.compute_Vs_scaled(); o.compute_Vx()
-    ws, wn = o.compute_WF(sample=False)
-    o32 = dict(mask=np.stack([ws, wn]), S_hat=ws * o.X, N_hat=wn * o.X)
-    o.M_step()
-    o32.update(g=o.g, cost=float(o.compute_expected_neg_log_like()))
-    if variant != "noNMF":
-        o32.update(W=o.W, H=o.H)
-    return ref, o32
-
-
-def _errors(got, ref):
-    """Per quantity: W, H, g, cost relative (largest over the elements), the masks absolute, S_hat / N_hat relative in L2."""
-    e = {}
-    for k, v in got.items():
-        if k == "mask":
-            e[k] = float(np.max(np.abs(np.asarray(v, np.float64) - ref[k])))
-        elif k in ("S_hat", "N_hat"):
-            e[k] = nrm_err(v, ref[k])
-        elif k == "cost":
-            e[k] = abs(float(v) - ref[k]) / abs(ref[k])
-        else:
-            e[k] = rel_err(v, ref[k])
-    return e
-
-
-def _bounds(e32):
-    return {k: max(FLOOR[k], E32_FACTOR * v) for k, v in e32.items()}
-
-
-def _violations(err, bound):
-    return [k for k in err if not err[k] <= bound[k]]
-
-
-def _fmt(err, bound=None):
-    return " ".join("%s %.2e" % (k, err[k]) + ("/%.1e" % bound[k] if bound else "") for k in err)
-
-
-def _case_inputs(F, K, R, variant):
-    """_inputs of tests/test_gpu_bin_counts.py (labels with M2 and the fixed noise PSD).  From 65 samples per frame up the
-    given samples are spread twice as wide: one row in 65 or 75 of the recipe's draws moves g by 3.0 to 3.5 bounds only
-    at rank 32 ((513, 32, 75), (529, 32, 65), (640, 32, 75)), short of the four the condition asks for; 4.5 and more so."""
-    c = _inputs(F, K, R, Dy=0 if variant == "M1" else 1)
-    if R >= 65:
-        c.Zs *= np.float32(2.0)
-    return c
-
-
-def _noise_psd(c):
-    return (np.random.default_rng(c.F).random((c.NT, c.F)) + 0.1).astype(np.float32)
-
-
 def _oracle_cpu(c, u, variant):
-    """The oracle of utterance u in the state of _inputs, with the variances of its samples from decoder_forward."""
+    """The oracle of utterance u in the state of es.inputs, with the variances of its samples from decoder_forward."""
     sl = slice(c.off[u], c.off[u + 1])
     if variant == "noNMF":
-        o = orc.MCEMOracleNoNMF(c.Xs[u], _noise_psd(c)[sl], c.gains[sl], c.Z0[sl], c.ys[u], c.params, 1, orc.NumpyRNG(0))
+        o = orc.MCEMOracleNoNMF(c.Xs[u], es.noise_psd(c)[sl], c.gains[sl], c.Z0[sl], c.ys[u], c.params, 1, orc.NumpyRNG(0))
     else:
         o = orc.MCEMOracle("M2" if c.Dy else "M1", 1)
         o.init_parameters(c.Xs[u], c.params, c.K, 1e-8, orc.NumpyRNG(0), y=c.ys[u], W0=c.W0[u], H0=c.H0[u])
@@ -414,20 +258,20 @@ def _edge_rows(F, K, R, variant):
 def _cpu_case(F, K, R, variant):
     """Per utterance: e32 (float32 oracle against the float64 formulas), the bounds, and per edge row the change of every
     quantity when that row is replaced by the one before it (row 0: by the last)."""
-    c = _case_inputs(F, K, R, variant)
+    c = es.case_inputs(F, K, R, variant)
     out = []
     for u in range(len(COUNTS)):
         o = _oracle_cpu(c, u, variant)
         Vs = np.asarray(o.Vs, np.float64)
-        ref = _reference(o, variant, Vs64=Vs)[0]
+        ref = es.reference(o, variant, Vs64=Vs)[0]
         change = {}
         if R >= 2:
             for r in _edge_rows(F, K, R, variant):
                 bad = Vs.copy()
                 bad[r] = Vs[r - 1]
-                change[r] = _errors(_reference(o, variant, Vs64=bad)[0], ref)
-        e32 = _errors(_reference(o, variant)[1], ref)                     # (last: the oracle's M-step changes its state)
-        out.append((e32, _bounds(e32), change))
+                change[r] = es.errors(es.reference(o, variant, Vs64=bad)[0], ref)
+        e32 = es.errors(es.reference(o, variant)[1], ref)                     # (last: the oracle's M-step changes its state)
+        out.append((e32, es.bounds(e32), change))
     return out
 
 
@@ -444,14 +288,14 @@ def test_float64_formulas_agree_with_the_oracle():
             for k, v in e32.items():
                 worst[k] = max(worst.get(k, 0.0), v)
             assert max(e32.values()) < 1e-5, (case, e32)
-    print("float32 oracle against the float64 formulas, largest: " + _fmt(worst))
+    print("float32 oracle against the float64 formulas, largest: " + es.fmt(worst))
 
 
 def test_one_wrong_row_exceeds_the_bounds():
     """No GPU: the condition on the bound, and the sensitivity of the comparison.  For every case with R >= 2 and every
     edge row, a result computed from the samples with that one row replaced by its neighbour -- what a kernel gives that
     reads a wrong row, skips one or counts one twice -- changes g and the masks by at least four times the bound, and
-    _violations() reports it."""
+    es.violations() reports it."""
     tight = {}
     for case in _all_cases():
         if case[2] < 2:
@@ -459,71 +303,16 @@ def test_one_wrong_row_exceeds_the_bounds():
         for u, (e32, bound, change) in enumerate(_cpu_case(*case)):
             assert change, case
             for r, ch in change.items():
-                assert _violations(ch, bound), (case, u, r, ch, bound)
+                assert es.violations(ch, bound), (case, u, r, ch, bound)
                 for k in ("g", "mask"):
                     assert bound[k] <= ch[k] / 4, (case, u, r, k, ch[k], bound[k])
                 for k in ch:
                     tight[k] = min(tight.get(k, np.inf), ch[k] / bound[k])
-    print("smallest change of one wrong row over its bound: " + _fmt(tight))
+    print("smallest change of one wrong row over its bound: " + es.fmt(tight))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # the kernels
-def _prepare(c, variant, precision, Rcap):
-    eng = _engine(c, precision, Rcap=Rcap, seeds=[3, 4, 5])
-    Vb = None
-    if variant == "noNMF":
-        Vb = _noise_psd(c)
-        Vbp = torch.zeros(eng.NT, eng.Fs)
-        Vbp[:, :c.F] = torch.from_numpy(Vb)
-        eng.set_noise_psd(Vbp.cuda())
-    return eng, Vb
-
-
-def _reset(c, eng):
-    eng.init_nmf(c.W0, c.H0)
-    eng.g.copy_(torch.from_numpy(c.gains))
-    eng.Z.copy_(torch.from_numpy(c.Z0))
-
-
-def _oracles_from(c, eng, variant, Vb, V):
-    """The oracles in the engine's present state, holding the variances V [NT, R, F] the device produced."""
-    out = []
-    for u in range(len(COUNTS)):
-        sl = eng.utt_slice(u)
-        if variant == "noNMF":
-            o = orc.MCEMOracleNoNMF(c.Xs[u], Vb[sl], eng.g[sl].cpu().numpy(), c.Z0[sl], c.ys[u], c.params, 1, orc.NumpyRNG(0))
-        else:
-            o = _oracle_at(c, eng, u)
-        o.Vs = np.ascontiguousarray(np.moveaxis(V[sl], 0, -1))           # (R, F, N)
-        out.append(o)
-    return out
-
-
-def _device_wiener(c, eng, u, out):
-    S, Nn, WFs, WFn = out
-    sl, F = eng.utt_slice(u), c.F
-    cplx = lambda t: np.ascontiguousarray(t[sl, :F].cpu().numpy()).view(np.complex64)[..., 0].T
-    return dict(mask=np.stack([WFs[sl, :F].cpu().numpy().T, WFn[sl, :F].cpu().numpy().T]), S_hat=cplx(S), N_hat=cplx(Nn))
-
-
-def _device_m_step(c, eng, u, cost, variant):
-    sl = eng.utt_slice(u)
-    d = dict(g=eng.g[sl].cpu().numpy(), cost=cost[u])
-    if variant != "noNMF":
-        d.update(W=eng.W[u, :c.F, :c.K].cpu().numpy(), H=eng.Ht[sl, :c.K].cpu().numpy().T)
-    return d
-
-
-def _compare(tag, refs, got_of, failures):
-    """Print every figure with its bound; collect what exceeds it (asserted at the end of the case, after every figure)."""
-    for u, (ref, o32) in enumerate(refs):
-        got = got_of(u)
-        err, bound = _errors(got, ref), _bounds(_errors({k: o32[k] for k in got}, ref))
-        print("%s utt %d: %s" % (tag, u, _fmt(err, bound)))
-        failures += [(tag, u, k, err[k], bound[k]) for k in _violations(err, bound)]
-
-
 @gpu
 @pytest.mark.parametrize("precision", PRECISIONS)
 @pytest.mark.parametrize("F,K,R,variant", STORED_CASES)
@@ -532,19 +321,19 @@ def test_stored_kernels_against_the_oracle_from_the_stored_rows(F, K, R, variant
     eng.decode of the chain's samples (the bounds of test_sample_store_holds_the_samples_variances); then wiener_stored and
     m_step_stored -- with every W-statistics kernel the shape has -- against the float64 formulas fed with the stored rows."""
     need_gpu()
-    c = _case_inputs(F, K, R, variant)
-    shp = shape_class(F, K, precision, N_WAVE_TILES, R, _n_cus())
-    runs = _stored_runs(F, K, R, variant, precision, _n_cus())
-    eng, Vb = _prepare(c, variant, precision, R)
-    assert eng.Fs == shp["Fs"] == _query(eng, "Q_FS") and eng.Kp == shp["Kp"] == _query(eng, "Q_KP") == runs[0][1]["hg"]["KP"]
-    assert _query(eng, "Q_MSTEP_PATH") == 0                               # (no fused run: the path is the caller's here)
+    c = es.case_inputs(F, K, R, variant)
+    shp = shape_class(F, K, precision, N_WAVE_TILES, R, es.n_cus())
+    runs = _stored_runs(F, K, R, variant, precision, es.n_cus())
+    eng, Vb = es.prepare(c, variant, precision, R)
+    assert eng.Fs == shp["Fs"] == es.query(eng, "Q_FS") and eng.Kp == shp["Kp"] == es.query(eng, "Q_KP") == runs[0][1]["hg"]["KP"]
+    assert es.query(eng, "Q_MSTEP_PATH") == 0                               # (no fused run: the path is the caller's here)
     eng.sample_store(True)
     failures = []
     for call, bi in enumerate(BURNINS(R)):
         tag = "stored %s F=%d K=%d R=%d %s bi=%d" % (precision, F, K, R, variant, bi)
-        _reset(c, eng)
+        es.reset(c, eng)
         eng.mh_chain(R, bi, 0.01, call=call)
-        assert _query(eng, "Q_CHAIN_KERNEL") == shp["chain_kernel"]
+        assert es.query(eng, "Q_CHAIN_KERNEL") == shp["chain_kernel"]
         V = eng.stored_variances(R).cpu().numpy()
         assert np.all(np.isfinite(V)) and np.all(V[:, :, :F] > 0)
         B1 = eng.B1
@@ -561,22 +350,22 @@ def test_stored_kernels_against_the_oracle_from_the_stored_rows(F, K, R, variant
         assert e[0] < (2e-5 if precision == "bf16x3" else 4e-3) and e[1] < (2e-5 if precision == "bf16x3" else 5e-2), (tag, e)
         if R >= 2:      # the rows are told apart: neighbouring samples' variances differ by far more than those bounds
             assert float(np.max(np.abs(V[:, 1:, :F] - V[:, :-1, :F]) / V[:, 1:, :F])) > 0.1
-        refs = [_reference(o, variant) for o in _oracles_from(c, eng, variant, Vb, V[:, :, :F])]
+        refs = [es.reference(o, variant) for o in es.oracles_from(c, eng, variant, Vb, V[:, :, :F])]
         out = eng.wiener_stored(want_masks=True)
-        _compare(tag + " wiener", refs, lambda u: _device_wiener(c, eng, u, out), failures)
-        _padding_is_zero(eng, out[2], out[3], out[0].abs().sum(-1), out[1].abs().sum(-1))
+        es.compare(tag + " wiener", refs, lambda u: es.device_wiener(c, eng, u, out), failures)
+        es.padding_is_zero(eng, out[2], out[3], out[0].abs().sum(-1), out[1].abs().sum(-1))
         pre = [t.clone() for t in (eng.W, eng.Ht, eng.g)]
         for env, sc, w_fused in runs:
-            with _env(**env):
+            with es.env(**env):
                 for t, p in zip((eng.W, eng.Ht, eng.g), pre):
                     t.copy_(p)
                 eng.m_step_stored()
                 if variant != "noNMF":
-                    assert _query(eng, "Q_W_FUSED") == w_fused, (tag, env)
+                    assert es.query(eng, "Q_W_FUSED") == w_fused, (tag, env)
             cost = eng.cost_from_frames(R)
             name = sc["wstats"]["kernel"] if sc["wstats"] else "gains only"
-            _compare(tag + " m-step (%s)" % name, refs, lambda u: _device_m_step(c, eng, u, cost, variant), failures)
-            _padding_is_zero(eng)
+            es.compare(tag + " m-step (%s)" % name, refs, lambda u: es.device_m_step(c, eng, u, cost, variant), failures)
+            es.padding_is_zero(eng)
     eng.sample_store(False)
     assert not failures, failures
 
@@ -590,16 +379,16 @@ def test_decoding_kernels_against_the_oracle_from_the_decoded_variances(F, K, R,
     decode_kernel decodes through the same routine (decode_tiles; the odd last bin through nyq_logit in every mode), so
     the variances of mode STORE are the ones modes WSTATS / HG / G / WF use."""
     need_gpu()
-    c = _case_inputs(F, K, R, variant)
+    c = es.case_inputs(F, K, R, variant)
     dc = decode_class(F, K, R, precision)
-    eng, Vb = _prepare(c, variant, precision, Rcap)
-    assert eng.Fs == _query(eng, "Q_FS") == (F + 15) // 16 * 16 and eng.Kp == _query(eng, "Q_KP") == dc["KP"]
+    eng, Vb = es.prepare(c, variant, precision, Rcap)
+    assert eng.Fs == es.query(eng, "Q_FS") == (F + 15) // 16 * 16 and eng.Kp == es.query(eng, "Q_KP") == dc["KP"]
     eng.Zs.fill_(100.0)                                                    # (a sample read beyond the count would show)
     eng.Zs[:, :R].copy_(torch.from_numpy(c.Zs))
     tag = "decoding %s F=%d K=%d R=%d/%d %s" % (precision, F, K, R, Rcap, variant)
     V = eng.decode(R).cpu().numpy()
     assert np.all(np.isfinite(V)) and np.all(V[:, :, F:] == 0)
-    oracles = _oracles_from(c, eng, variant, Vb, V[:, :, :F])
+    oracles = es.oracles_from(c, eng, variant, Vb, V[:, :, :F])
     for u, o in enumerate(oracles):
         sl = eng.utt_slice(u)
         mine = o.Vs
@@ -608,13 +397,13 @@ def test_decoding_kernels_against_the_oracle_from_the_decoded_variances(F, K, R,
         print("%s utt %d: decode %.2e" % (tag, u, e))
         assert e < (2e-4 if precision == "bf16x3" else 5e-2), (tag, u, e)
         o.Vs = mine
-    refs = [_reference(o, variant) for o in oracles]
+    refs = [es.reference(o, variant) for o in oracles]
     failures = []
     out = eng.wiener(R, want_masks=True)
-    _compare(tag + " wiener", refs, lambda u: _device_wiener(c, eng, u, out), failures)
-    _padding_is_zero(eng, out[2], out[3], out[0].abs().sum(-1), out[1].abs().sum(-1))
+    es.compare(tag + " wiener", refs, lambda u: es.device_wiener(c, eng, u, out), failures)
+    es.padding_is_zero(eng, out[2], out[3], out[0].abs().sum(-1), out[1].abs().sum(-1))
     eng.m_step(R)
     cost = eng.cost_from_frames(R)
-    _compare(tag + " m-step", refs, lambda u: _device_m_step(c, eng, u, cost, variant), failures)
-    _padding_is_zero(eng)
+    es.compare(tag + " m-step", refs, lambda u: es.device_m_step(c, eng, u, cost, variant), failures)
+    es.padding_is_zero(eng)
     assert not failures, failures

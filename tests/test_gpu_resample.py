@@ -12,7 +12,7 @@ import torch
 import resample_cases as rc
 import vaenmf_oracle as orc
 from guarded import Arena, same_bits
-from test_gpu_parity import need_gpu
+from helpers import need_gpu
 
 pytestmark = pytest.mark.gpu
 

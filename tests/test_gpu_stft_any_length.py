@@ -8,15 +8,11 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import vaenmf_oracle as orc
-from helpers import GOLDEN, nrm_err
-from test_stft_any_length_cpu import ref_istft, ref_stft
+from em_support import RecordingRNG
+from helpers import GOLDEN, need_gpu, nrm_err
+from stft_cases import ref_istft, ref_stft
 
 SIZES = (17, 320, 400, 441, 480, 800, 801, 1000, 1031, 1280, 1536, 2401, 3840, 4093, 4096)
-
-
-def need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
 
 
 def _speech():
@@ -125,19 +121,6 @@ def test_ragged_batch_equals_single_calls():
         o += nfr
 
 
-class _Recorder:
-    def __init__(self, seed):
-        self.g, self.draws = orc.NumpyRNG(seed), []
-
-    def rand(self, *shape):
-        self.draws.append(self.g.rand(*shape))
-        return self.draws[-1]
-
-    def randn(self, *shape):
-        self.draws.append(self.g.randn(*shape))
-        return self.draws[-1]
-
-
 def test_mcem_at_the_reference_default_window():
     """stft (F = 401, the team chain kernel at 26 bin tiles) -> MCEM_M1 with replayed draws -> istft, against the oracle
     run on the oracle's STFT with the same draws (bounds of test_full_run_replay)."""
@@ -148,7 +131,7 @@ def test_mcem_at_the_reference_default_window():
     F, K, niter = 401, 10, 3
     params = orc.xavier_normal_params([F, 32, [128, 128]], seed=3)
     Xo = orc.stft(x, fs=16000, wlen_sec=50e-3).T                       # (N, F)
-    rec = _Recorder(7)
+    rec = RecordingRNG(7)
     o = orc.MCEMOracle("M1", niter, 10, 10, 10, 10, 0.01)
     o.init_parameters(Xo, params, K, 1e-8, rec)                         # records the draws it takes
     c_ref = o.run()

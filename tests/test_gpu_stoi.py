@@ -17,7 +17,7 @@ import torch
 
 import stoi_cases as sc
 from guarded import Arena
-from test_gpu_parity import need_gpu
+from helpers import need_gpu
 
 pytestmark = pytest.mark.gpu
 

@@ -28,7 +28,8 @@ import pytest
 import torch
 
 import vaenmf_oracle as orc
-from test_gpu_parity import dec_list, need_gpu
+from em_support import dec_list
+from helpers import need_gpu
 
 VAR_RW = 0.01
 NITER = 3

@@ -31,133 +31,22 @@ import pytest
 import torch
 
 import train_cases as tc
+import train_support as ts
 import vaenmf
 from guarded import Arena, same_bits
 from helpers import nrm_err
+from train_support import ACTS, DEV, FACTOR, U, gemm_forms_case
 from vaenmf import _lib
 from vaenmf import train as vt
 from vaenmf._lib import check, lib
 
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -24
-C_CHAIN = 1.5e-7
-FACTOR = 8.0
-DEV = "cuda:0"
-ACTS = {"none": _lib.ACT_NONE, "tanh": _lib.ACT_TANH, "relu": _lib.ACT_RELU, "exp": _lib.ACT_EXP, "sigmoid": _lib.ACT_SIGMOID}
 SIZES_M = (1, 15, 16, 17, 33, 128)
 SIZES_IO = (1, 16, 17, 33, 65, 66, 128, 130, 256)
 
 
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _st():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _put(arena, name, host, ld=None):
-    """A host matrix as an arena buffer with rows `ld` apart: the columns past its width stay poison.  Returns the buffer."""
-    host = np.asarray(host)
-    if host.ndim == 1 or ld is None or ld == host.shape[1]:
-        t = arena.carve(name, host.shape, torch.from_numpy(host).dtype)
-        t.copy_(torch.from_numpy(np.ascontiguousarray(host)))
-        return t
-    t = arena.carve(name, (host.shape[0], ld), torch.float32)
-    t[:, :host.shape[1]].copy_(torch.from_numpy(np.ascontiguousarray(host)))
-    return t
-
-
-def _out(arena, name, rows, cols, ld=None, dtype=torch.float32):
-    return arena.carve(name, (rows, ld or cols) if cols else (rows,), dtype)
-
-
-def _padding_untouched(arena, t, cols):
-    return t.dim() == 1 or t.shape[1] == cols or arena.is_poison(t[:, cols:])
-
-
 # ---------------------------------------------------------------------------------------------------------------- 1. GEMM
-def _act64(name, v):
-    return {"none": v, "tanh": np.tanh(v), "relu": np.maximum(v, 0.0), "exp": np.exp(v), "sigmoid": 1.0 / (1.0 + np.exp(-v))}[name]
-
-
-def _act_tol(name, pre, tol_pre):
-    val = np.abs(_act64(name, pre))
-    if name in ("none", "relu"):
-        return tol_pre
-    if name == "tanh":
-        return tol_pre + 4 * U * val
-    if name == "sigmoid":
-        return 0.25 * tol_pre + 4 * U * val
-    return val * np.expm1(tol_pre) + 4 * U * val
-
-
-def _saved_output(rng, name, shape):
-    """A previous layer's saved activated output in the activation's range, zeros and saturated units among them."""
-    v = rng.standard_normal(shape) * 1.5
-    y = _act64(name, v).astype(np.float32)
-    if name == "relu":
-        y[rng.random(shape) < 0.2] = 0.0
-    return y
-
-
-def _deriv64(name, y):
-    y = y.astype(np.float64)
-    return {"none": np.ones_like(y), "tanh": 1 - y * y, "relu": (y > 0).astype(np.float64), "exp": y, "sigmoid": y * (1 - y)}[name]
-
-
-def gemm_forms_case(rng, M, n_in, n_out, act, j, worst):
-    """Forward, dX, dW and db of one layer shape against float64, each element within its bound from the operands; the
-    largest error / bound of each form goes into `worst`.  (tests/test_gpu_train_shapes.py runs it at long reductions.)"""
-    ldx, ldw, ldy, ldz, ldp = n_in + 3, n_in + (j % 3), n_out + 5, n_out + 1, n_in + 2
-    X = rng.standard_normal((M, n_in)).astype(np.float32)
-    W = (rng.standard_normal((n_out, n_in)) / np.sqrt(n_in)).astype(np.float32)
-    b = (rng.standard_normal(n_out) * 0.3).astype(np.float32)
-    dZ = rng.standard_normal((M, n_out)).astype(np.float32)
-    dZ[rng.random((M, n_out)) < 0.05] = 0.0
-    Yp = _saved_output(rng, act, (M, n_in))
-    arena = Arena(8 << 20, "nan", device=DEV)
-    dX_, dW_, db_ = _put(arena, "X", X, ldx), _put(arena, "W", W, ldw), _put(arena, "b", b)
-    dZ_, Yp_ = _put(arena, "dZ", dZ, ldz), _put(arena, "Yp", Yp, ldp)
-    Y_ = _out(arena, "Y", M, n_out, ldy)
-    gX_ = _out(arena, "gX", M, n_in, ldx)
-    gW_ = _out(arena, "gW", n_out, n_in, ldw)
-    gb_ = _out(arena, "gb", n_out, 0)
-    arena.snapshot(["X", "W", "b", "dZ", "Yp"])
-    check(lib().vaenmf_train_dense_fwd(_p(dX_), M, n_in, ldx, _p(dW_), ldw, _p(db_), n_out, ACTS[act], _p(Y_), ldy, _st()))
-    check(lib().vaenmf_train_dense_dx(_p(dZ_), M, n_out, ldz, _p(dW_), ldw, n_in, _p(Yp_), ldp, ACTS[act], _p(gX_), ldx, _st()))
-    check(lib().vaenmf_train_dense_dw(_p(dZ_), M, n_out, ldz, _p(dX_), n_in, ldx, _p(gW_), ldw, _p(gb_), _st()))
-    torch.cuda.synchronize()
-    what = "M=%d in=%d out=%d act=%s" % (M, n_in, n_out, act)
-    arena.check(what)
-    arena.unchanged(what=what)
-    assert _padding_untouched(arena, Y_, n_out) and _padding_untouched(arena, gX_, n_in) and _padding_untouched(arena, gW_, n_in), what
-    X64, W64, dZ64 = X.astype(np.float64), W.astype(np.float64), dZ.astype(np.float64)
-    # forward
-    pre = X64 @ W64.T + b
-    tol = _act_tol(act, pre, C_CHAIN * (np.abs(X64) @ np.abs(W64).T + np.abs(b)))
-    err = np.abs(Y_[:, :n_out].cpu().numpy().astype(np.float64) - _act64(act, pre))
-    assert np.all(err <= tol), (what, "fwd", float((err / tol).max()))
-    worst["fwd"] = max(worst["fwd"], float((err / tol).max()))
-    # data gradient
-    acc, d = dZ64 @ W64, _deriv64(act, Yp)
-    ref = acc * d
-    tol = C_CHAIN * (np.abs(dZ64) @ np.abs(W64)) * np.abs(d) + 2 * U * np.abs(acc) + 2 * U * np.abs(ref)
-    err = np.abs(gX_[:, :n_in].cpu().numpy().astype(np.float64) - ref)
-    assert np.all(err <= tol), (what, "dx", float((err / np.maximum(tol, 1e-300)).max()))
-    worst["dx"] = max(worst["dx"], float((err / np.maximum(tol, 1e-300)).max()))
-    # weight gradient and bias gradient from the same pass
-    ref, tol = dZ64.T @ X64, C_CHAIN * (np.abs(dZ64).T @ np.abs(X64))
-    err = np.abs(gW_[:, :n_in].cpu().numpy().astype(np.float64) - ref)
-    assert np.all(err <= tol), (what, "dw", float((err / np.maximum(tol, 1e-300)).max()))
-    worst["dw"] = max(worst["dw"], float((err / np.maximum(tol, 1e-300)).max()))
-    ref, tol = dZ64.sum(0), C_CHAIN * np.abs(dZ64).sum(0)
-    err = np.abs(gb_.cpu().numpy().astype(np.float64) - ref)
-    assert np.all(err <= tol), (what, "db", float((err / np.maximum(tol, 1e-300)).max()))
-    worst["db"] = max(worst["db"], float((err / np.maximum(tol, 1e-300)).max()))
-
-
 @pytest.mark.parametrize("M", SIZES_M)
 def test_gemm_forms(M):
     rng = np.random.default_rng(700 + M)
@@ -177,8 +66,8 @@ def test_gemm_is_four_k_ordered_fmaf_chains():
     X = (rng.standard_normal((M, K)) * np.exp(rng.normal(0, 4, (M, K)))).astype(np.float32)
     W = (rng.standard_normal((N, K)) * np.exp(rng.normal(0, 4, (N, K)))).astype(np.float32)
     arena = Arena(2 << 20, "nan", device=DEV)
-    X_, W_, Y_ = _put(arena, "X", X, K + 1), _put(arena, "W", W, K + 2), _out(arena, "Y", M, N, N + 3)
-    check(lib().vaenmf_train_dense_fwd(_p(X_), M, K, K + 1, _p(W_), K + 2, None, N, _lib.ACT_NONE, _p(Y_), N + 3, _st()))
+    X_, W_, Y_ = ts.put(arena, "X", X, K + 1), ts.put(arena, "W", W, K + 2), ts.out(arena, "Y", M, N, N + 3)
+    check(lib().vaenmf_train_dense_fwd(ts.p(X_), M, K, K + 1, ts.p(W_), K + 2, None, N, _lib.ACT_NONE, ts.p(Y_), N + 3, ts.st()))
     torch.cuda.synchronize()
     arena.check("chain")
     c = [np.zeros((M, N), np.float32) for _ in range(4)]  # chain j takes the k with (k / 4) % 4 == j (include/vaenmf.h)
@@ -201,13 +90,13 @@ def test_gemm_is_four_k_ordered_fmaf_chains():
 
 def test_dense_entry_points_refuse_bad_arguments():
     t = torch.zeros(64, device=DEV)
-    assert lib().vaenmf_train_dense_fwd(_p(t), 0, 4, 4, _p(t), 4, None, 4, 0, _p(t), 4, _st()) == -1
-    assert lib().vaenmf_train_dense_fwd(_p(t), 2, 4, 3, _p(t), 4, None, 4, 0, _p(t), 4, _st()) == -1          # ldx < in
-    assert lib().vaenmf_train_dense_fwd(_p(t), 2, 4, 4, _p(t), 4, None, 4, _lib.ACT_STEP, _p(t), 4, _st()) == -1
-    assert lib().vaenmf_train_dense_dx(_p(t), 2, 4, 4, _p(t), 4, 4, None, 0, _lib.ACT_TANH, _p(t), 4, _st()) == -1   # tanh' needs Yprev
-    assert lib().vaenmf_train_dense_dw(_p(t), 2, 4, 4, _p(t), 5000, 5000, _p(t), 5000, None, _st()) == -1
+    assert lib().vaenmf_train_dense_fwd(ts.p(t), 0, 4, 4, ts.p(t), 4, None, 4, 0, ts.p(t), 4, ts.st()) == -1
+    assert lib().vaenmf_train_dense_fwd(ts.p(t), 2, 4, 3, ts.p(t), 4, None, 4, 0, ts.p(t), 4, ts.st()) == -1          # ldx < in
+    assert lib().vaenmf_train_dense_fwd(ts.p(t), 2, 4, 4, ts.p(t), 4, None, 4, _lib.ACT_STEP, ts.p(t), 4, ts.st()) == -1
+    assert lib().vaenmf_train_dense_dx(ts.p(t), 2, 4, 4, ts.p(t), 4, 4, None, 0, _lib.ACT_TANH, ts.p(t), 4, ts.st()) == -1   # tanh' needs Yprev
+    assert lib().vaenmf_train_dense_dw(ts.p(t), 2, 4, 4, ts.p(t), 5000, 5000, ts.p(t), 5000, None, ts.st()) == -1
     assert b"outside" in lib().vaenmf_last_error()
-    assert lib().vaenmf_adam(_p(t), _p(t), _p(t), _p(t), 4, 0, 1e-3, 0.9, 0.999, 1e-8, _st()) == -1            # the first step is 1
+    assert lib().vaenmf_adam(ts.p(t), ts.p(t), ts.p(t), ts.p(t), 4, 0, 1e-3, 0.9, 0.999, 1e-8, ts.st()) == -1            # the first step is 1
 
 
 # ---------------------------------------------------------------------------------------------------------------- 2. heads
@@ -223,18 +112,18 @@ def test_elbo_head(B):
     e = rng.standard_normal((B, z)).astype(np.float32)
     dz = rng.standard_normal((B, z)).astype(np.float32)
     arena = Arena(4 << 20, "nan", device=DEV)
-    x_, a_, ml_, e_, dz_ = _put(arena, "x", x, F + 2), _put(arena, "a", a, F + 1), _put(arena, "ml", ml, 2 * z + 3), _put(arena, "e", e), _put(arena, "dz", dz, z + 1)
-    dA_, Z_, dML_ = _out(arena, "dA", B, F, F + 4), _out(arena, "Z", B, z, z + 5), _out(arena, "dML", B, 2 * z, 2 * z + 1)
-    rr_, rk_, out_ = _out(arena, "rr", B, 0, dtype=torch.float64), _out(arena, "rk", B, 0, dtype=torch.float64), _out(arena, "out", 8, 0, dtype=torch.float64)
+    x_, a_, ml_, e_, dz_ = ts.put(arena, "x", x, F + 2), ts.put(arena, "a", a, F + 1), ts.put(arena, "ml", ml, 2 * z + 3), ts.put(arena, "e", e), ts.put(arena, "dz", dz, z + 1)
+    dA_, Z_, dML_ = ts.out(arena, "dA", B, F, F + 4), ts.out(arena, "Z", B, z, z + 5), ts.out(arena, "dML", B, 2 * z, 2 * z + 1)
+    rr_, rk_, out_ = ts.out(arena, "rr", B, 0, dtype=torch.float64), ts.out(arena, "rk", B, 0, dtype=torch.float64), ts.out(arena, "out", 8, 0, dtype=torch.float64)
     arena.snapshot(["x", "a", "ml", "e", "dz"])
-    check(lib().vaenmf_elbo_out(_p(x_), F + 2, _p(a_), F + 1, B, F, eps, _p(dA_), F + 4, _p(rr_), _st()))
-    check(lib().vaenmf_elbo_latent_fwd(_p(ml_), 2 * z + 3, _p(e_), B, z, _p(Z_), z + 5, _st()))
-    check(lib().vaenmf_elbo_latent_bwd(_p(ml_), 2 * z + 3, _p(e_), _p(dz_), z + 1, B, z, _p(dML_), 2 * z + 1, _p(rk_), _st()))
-    check(lib().vaenmf_loss_reduce(_p(rr_), _p(rk_), None, B, _p(out_), _st()))
+    check(lib().vaenmf_elbo_out(ts.p(x_), F + 2, ts.p(a_), F + 1, B, F, eps, ts.p(dA_), F + 4, ts.p(rr_), ts.st()))
+    check(lib().vaenmf_elbo_latent_fwd(ts.p(ml_), 2 * z + 3, ts.p(e_), B, z, ts.p(Z_), z + 5, ts.st()))
+    check(lib().vaenmf_elbo_latent_bwd(ts.p(ml_), 2 * z + 3, ts.p(e_), ts.p(dz_), z + 1, B, z, ts.p(dML_), 2 * z + 1, ts.p(rk_), ts.st()))
+    check(lib().vaenmf_loss_reduce(ts.p(rr_), ts.p(rk_), None, B, ts.p(out_), ts.st()))
     torch.cuda.synchronize()
     arena.check("elbo B=%d" % B)
     arena.unchanged(what="elbo")
-    assert _padding_untouched(arena, dA_, F) and _padding_untouched(arena, Z_, z) and _padding_untouched(arena, dML_, 2 * z)
+    assert ts.padding_untouched(arena, dA_, F) and ts.padding_untouched(arena, Z_, z) and ts.padding_untouched(arena, dML_, 2 * z)
     x64, a64 = x.astype(np.float64), a.astype(np.float64)
     q = x64 / np.exp(a64)
     terms = [q, np.log(x64 + eps), a64, np.ones_like(a64)]
@@ -258,7 +147,7 @@ def test_elbo_head(B):
     assert np.array_equal(out_[4:].cpu().view(torch.int64).numpy(), np.zeros(4, np.int64))
     # evaluation: no gradient buffers, the same sums
     rr2 = torch.full_like(rr_, float("nan"))
-    check(lib().vaenmf_elbo_out(_p(x_), F + 2, _p(a_), F + 1, B, F, eps, None, 0, _p(rr2), _st()))
+    check(lib().vaenmf_elbo_out(ts.p(x_), F + 2, ts.p(a_), F + 1, B, F, eps, None, 0, ts.p(rr2), ts.st()))
     assert same_bits(rr2, rr_)
 
 
@@ -272,15 +161,15 @@ def test_bce_head(B):
     y = (rng.random((B, D)) < 0.5).astype(np.float32)
     y[0, :6] = [1, 1, 0, 0, 0, 1]
     arena = Arena(4 << 20, "nan", device=DEV)
-    a_, y_ = _put(arena, "a", a, D + 3), _put(arena, "y", y, D + 1)
-    dA_, rl_, rc_, out_ = _out(arena, "dA", B, D, D + 2), _out(arena, "rl", B, 0, dtype=torch.float64), _out(arena, "rc", B, 4, dtype=torch.int32), _out(arena, "out", 8, 0, dtype=torch.float64)
+    a_, y_ = ts.put(arena, "a", a, D + 3), ts.put(arena, "y", y, D + 1)
+    dA_, rl_, rc_, out_ = ts.out(arena, "dA", B, D, D + 2), ts.out(arena, "rl", B, 0, dtype=torch.float64), ts.out(arena, "rc", B, 4, dtype=torch.int32), ts.out(arena, "out", 8, 0, dtype=torch.float64)
     arena.snapshot(["a", "y"])
-    check(lib().vaenmf_bce_head(_p(a_), D + 3, _p(y_), D + 1, B, D, eps, _p(dA_), D + 2, _p(rl_), _p(rc_), _st()))
-    check(lib().vaenmf_loss_reduce(_p(rl_), None, _p(rc_), B, _p(out_), _st()))
+    check(lib().vaenmf_bce_head(ts.p(a_), D + 3, ts.p(y_), D + 1, B, D, eps, ts.p(dA_), D + 2, ts.p(rl_), ts.p(rc_), ts.st()))
+    check(lib().vaenmf_loss_reduce(ts.p(rl_), None, ts.p(rc_), B, ts.p(out_), ts.st()))
     torch.cuda.synchronize()
     arena.check("bce B=%d" % B)
     arena.unchanged(what="bce")
-    assert _padding_untouched(arena, dA_, D)
+    assert ts.padding_untouched(arena, dA_, D)
     a64, y64 = a.astype(np.float64), y.astype(np.float64)
     ex = np.exp(-np.abs(a64))
     big, small = 1 / (1 + ex), ex / (1 + ex)
@@ -322,13 +211,13 @@ def test_adam():
     pt = torch.tensor(p0.copy(), requires_grad=True)
     opt = torch.optim.Adam([pt], lr=lr, betas=(0.9, 0.999), eps=1e-8)
     arena = Arena(4 << 20, "nan", device=DEV)
-    p_, g_, m_, v_ = _put(arena, "p", p0), _out(arena, "g", n, 0), _out(arena, "m", n, 0), _out(arena, "v", n, 0)
+    p_, g_, m_, v_ = ts.put(arena, "p", p0), ts.out(arena, "g", n, 0), ts.out(arena, "m", n, 0), ts.out(arena, "v", n, 0)
     m_.zero_(); v_.zero_()
     for s in range(steps):
         pt.grad = torch.tensor(g[s].copy())
         opt.step()
         g_.copy_(torch.from_numpy(g[s]))
-        check(lib().vaenmf_adam(_p(p_), _p(g_), _p(m_), _p(v_), n, s + 1, lr, 0.9, 0.999, 1e-8, _st()))
+        check(lib().vaenmf_adam(ts.p(p_), ts.p(g_), ts.p(m_), ts.p(v_), n, s + 1, lr, 0.9, 0.999, 1e-8, ts.st()))
     torch.cuda.synchronize()
     arena.check("adam")
     got, ref = p_.cpu().numpy(), pt.detach().numpy()
@@ -346,29 +235,6 @@ def test_adam():
 
 
 # ---------------------------------------------------------------------------------------------------------------- 4. steps
-def _gpu_run(case, init, data, steps=tc.STEPS, eps_mode="replay", seed=0):
-    model = tc.make_model(case)
-    model.load_state_dict(init)
-    tr = vt.Trainer(model, max_batch=case.B, seed=seed, device=DEV)
-    tr.bind(data["X"].T, None if data["Y"] is None else data["Y"].T)
-    if case.kind == "Classifier":
-        tr.set_norm(data["mean"], data["std"], tc.LOSS_EPS)
-    rows = torch.zeros(steps, 8, dtype=torch.float64, device=DEV)
-    grad1 = None
-    for s in range(steps):
-        eps = data["eps"][s] if (data["eps"] is not None and eps_mode == "replay") else None
-        if eps_mode == "fill" and case.kind != "Classifier":
-            eps = tr.eps_fill(s + 1, case.B)
-        tr.step(data["idx"][s], eps=eps, out=rows[s])
-        if s == 0:
-            grad1 = {k: v.numpy() for k, v in tr.gradients().items()}
-    r = vt.read_losses(rows)
-    losses = np.stack([r["loss"], r["recon"], r["kl"]], 1)
-    counts = np.stack([r["tp"], r["tn"], r["fp"], r["fn"]], 1)
-    final = {k: v.numpy() for k, v in tr.state_dict().items()}
-    return tr, tc.Run(losses, counts, grad1, final)
-
-
 STEP_CASES = [tc.GOLDEN_CASES[k] for k in sorted(tc.GOLDEN_CASES)] + [tc.sweep_case(kind, B) for kind in ("M1", "M2", "Classifier") for B in tc.SWEEP_B]
 
 
@@ -390,7 +256,7 @@ def test_step_and_trajectory(case):
     and 3.9e-7.  So this ratio is that of two heavy-tailed numbers, and it moves with the summation order: with the chains
     added as (c0 + c1) + (c2 + c3) instead of by two-sums the same case came out at 8.34 with gradients at 0.6."""
     init, data, r64, r32 = tc.reference_runs(case)
-    tr, got = _gpu_run(case, init, data)
+    tr, got = ts.gpu_run(case, init, data)
     worst = {"grad1": 0.0, "final": 0.0}
     fails = []
     for k in r64.final:
@@ -422,10 +288,10 @@ def test_step_and_trajectory(case):
 def test_reproducible_and_device_draws():
     case = tc.GOLDEN_CASES["train_m2_vad_f65"]
     init, data, _, _ = tc.reference_runs(case)
-    tr1, a = _gpu_run(case, init, data, eps_mode="device", seed=7)
-    _, b = _gpu_run(case, init, data, eps_mode="device", seed=7)
-    _, c = _gpu_run(case, init, data, eps_mode="fill", seed=7)
-    _, d = _gpu_run(case, init, data, eps_mode="device", seed=8)
+    tr1, a = ts.gpu_run(case, init, data, eps_mode="device", seed=7)
+    _, b = ts.gpu_run(case, init, data, eps_mode="device", seed=7)
+    _, c = ts.gpu_run(case, init, data, eps_mode="fill", seed=7)
+    _, d = ts.gpu_run(case, init, data, eps_mode="device", seed=8)
     for k in a.final:
         assert np.array_equal(a.final[k].view(np.int32), b.final[k].view(np.int32)), "the same seed twice: %s differs" % k
         assert np.array_equal(a.final[k].view(np.int32), c.final[k].view(np.int32)), "replay of eps_fill: %s differs" % k

@@ -41,7 +41,8 @@ import torch
 import train_cases as tc
 from guarded import Arena, bits, same_bits
 from helpers import nrm_err
-from test_gpu_train import ACTS, DEV, FACTOR, U, _gpu_run, _out, _p, _put, _st, gemm_forms_case
+import train_support as ts
+from train_support import ACTS, DEV, FACTOR, U, gemm_forms_case
 from vaenmf import _lib
 from vaenmf import train as vt
 from vaenmf._lib import check, lib
@@ -77,7 +78,7 @@ def test_shapes_step_and_trajectory(name):
     1.00 .. 1.26 (m2_wide), losses 0.01 .. 0.44."""
     case = tc.SHAPE_CASES[name]
     init, data, r64, r32 = tc.reference_runs(case)
-    tr, got = _gpu_run(case, init, data)
+    tr, got = ts.gpu_run(case, init, data)
     wg, fg = _hold_tensors(case, "grad1", got, r64, r32)
     wf, ff = _hold_tensors(case, "final", got, r64, r32)
     ncol = 1 if case.kind == "Classifier" else 3
@@ -254,7 +255,7 @@ def test_resume():
     n = lib().vaenmf_trainer_num_tensors(h)
     assert n == len(resumed.keys) == 14
     for which, i, word in ((-1, 0, b"which=-1"), (4, 0, b"which=4"), (_lib.TRAIN_ADAM_M, n, b"tensor 14 of 14"), (_lib.TRAIN_ADAM_V, -1, b"tensor -1 of 14")):
-        assert lib().vaenmf_trainer_set_tensor(h, which, i, _p(t), _st()) == -1 and word in lib().vaenmf_last_error(), (which, i)
+        assert lib().vaenmf_trainer_set_tensor(h, which, i, ts.p(t), ts.st()) == -1 and word in lib().vaenmf_last_error(), (which, i)
     assert _same_state(b, _state(resumed))
 
 
@@ -285,12 +286,12 @@ def test_gather(B):
             for norm in (False, True):
                 what = "B=%d ncol=%d col0=%d norm=%s" % (B, ncol, col0, norm)
                 arena = Arena(4 << 20, "nan", device=DEV)
-                src_, idx_ = _put(arena, "src", src, lds), _put(arena, "idx", idx)
-                mean_, std_ = _put(arena, "mean", mean), _put(arena, "std", std)
-                dst_ = _out(arena, "dst", B, ldd, ldd)
+                src_, idx_ = ts.put(arena, "src", src, lds), ts.put(arena, "idx", idx)
+                mean_, std_ = ts.put(arena, "mean", mean), ts.put(arena, "std", std)
+                dst_ = ts.out(arena, "dst", B, ldd, ldd)
                 arena.snapshot(["src", "idx", "mean", "std"])
-                check(lib().vaenmf_train_gather(_p(src_), lds, NT, _p(idx_), B, ncol, _p(mean_) if norm else None, _p(std_) if norm else None,
-                                                eps if norm else 0.0, _p(dst_), ldd, col0, _st()))
+                check(lib().vaenmf_train_gather(ts.p(src_), lds, NT, ts.p(idx_), B, ncol, ts.p(mean_) if norm else None, ts.p(std_) if norm else None,
+                                                eps if norm else 0.0, ts.p(dst_), ldd, col0, ts.st()))
                 torch.cuda.synchronize()
                 arena.check(what)
                 arena.unchanged(what=what)
@@ -321,11 +322,11 @@ def test_gather_rows_outside_and_refusals():
     inside = idx[[0, 2, 4]]
     for poison, norm in ((p, n) for p in ("nan", "1e30") for n in (False, True)):
         arena = Arena(2 << 20, poison, device=DEV)
-        src_, idx_, mean_, std_ = _put(arena, "src", src, lds), _put(arena, "idx", idx), _put(arena, "mean", mean), _put(arena, "std", std)
-        dst_ = _out(arena, "dst", len(idx), ldd, ldd)
+        src_, idx_, mean_, std_ = ts.put(arena, "src", src, lds), ts.put(arena, "idx", idx), ts.put(arena, "mean", mean), ts.put(arena, "std", std)
+        dst_ = ts.out(arena, "dst", len(idx), ldd, ldd)
         arena.snapshot(["src", "idx", "mean", "std"])
-        check(lib().vaenmf_train_gather(_p(src_), lds, NT, _p(idx_), len(idx), ncol, _p(mean_) if norm else None, _p(std_) if norm else None,
-                                        1e-8 if norm else 0.0, _p(dst_), ldd, col0, _st()))
+        check(lib().vaenmf_train_gather(ts.p(src_), lds, NT, ts.p(idx_), len(idx), ncol, ts.p(mean_) if norm else None, ts.p(std_) if norm else None,
+                                        1e-8 if norm else 0.0, ts.p(dst_), ldd, col0, ts.st()))
         torch.cuda.synchronize()
         arena.check("rows outside")
         arena.unchanged(what="rows outside")
@@ -340,10 +341,10 @@ def test_gather_rows_outside_and_refusals():
             assert np.all(np.abs(got[[0, 2, 4]] - ref) <= 4 * U * np.abs(ref))
     t, i = torch.zeros(64, device=DEV), torch.zeros(4, dtype=torch.int32, device=DEV)
     g = lib().vaenmf_train_gather
-    assert g(_p(t), 3, 4, _p(i), 2, 4, None, None, 0.0, _p(t), 8, 0, _st()) == -1 and b"lds=3 < ncol=4" in lib().vaenmf_last_error()
-    assert g(_p(t), 4, 4, _p(i), 2, 4, None, None, 0.0, _p(t), 8, 5, _st()) == -1 and b"[5, 9) outside ldd=8" in lib().vaenmf_last_error()
-    assert g(_p(t), 4, 4, _p(i), 2, 4, _p(t), None, 0.0, _p(t), 8, 0, _st()) == -1 and b"go together" in lib().vaenmf_last_error()
-    assert g(_p(t), 4, 0, _p(i), 2, 4, None, None, 0.0, _p(t), 8, 0, _st()) == -1 and b"NT=0" in lib().vaenmf_last_error()
+    assert g(ts.p(t), 3, 4, ts.p(i), 2, 4, None, None, 0.0, ts.p(t), 8, 0, ts.st()) == -1 and b"lds=3 < ncol=4" in lib().vaenmf_last_error()
+    assert g(ts.p(t), 4, 4, ts.p(i), 2, 4, None, None, 0.0, ts.p(t), 8, 5, ts.st()) == -1 and b"[5, 9) outside ldd=8" in lib().vaenmf_last_error()
+    assert g(ts.p(t), 4, 4, ts.p(i), 2, 4, ts.p(t), None, 0.0, ts.p(t), 8, 0, ts.st()) == -1 and b"go together" in lib().vaenmf_last_error()
+    assert g(ts.p(t), 4, 0, ts.p(i), 2, 4, None, None, 0.0, ts.p(t), 8, 0, ts.st()) == -1 and b"NT=0" in lib().vaenmf_last_error()
     torch.cuda.synchronize()
     assert not t.any()
 
@@ -408,9 +409,9 @@ def test_adam_single_late_steps(step):
     opt.step()
     assert opt.state[pt]["step"].item() == step
     arena = Arena(4 << 20, "nan", device=DEV)
-    p_, g_, m_, v_ = _put(arena, "p", p0), _put(arena, "g", g), _put(arena, "m", m0), _put(arena, "v", v0)
+    p_, g_, m_, v_ = ts.put(arena, "p", p0), ts.put(arena, "g", g), ts.put(arena, "m", m0), ts.put(arena, "v", v0)
     arena.snapshot(["g"])
-    check(lib().vaenmf_adam(_p(p_), _p(g_), _p(m_), _p(v_), n, step, lr, b1, b2, 1e-8, _st()))
+    check(lib().vaenmf_adam(ts.p(p_), ts.p(g_), ts.p(m_), ts.p(v_), n, step, lr, b1, b2, 1e-8, ts.st()))
     torch.cuda.synchronize()
     arena.check("adam step %d" % step)
     arena.unchanged(what="adam")

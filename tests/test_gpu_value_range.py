@@ -103,9 +103,9 @@ import pytest
 import torch
 
 import value_cases as vc
-from test_gpu_bin_counts import _padding_is_zero, _query
-from test_gpu_parity import make_engine, need_gpu
-from test_gpu_rank_and_samples import _bounds, _device_m_step, _device_wiener, _errors, _oracles_from, _reference, _violations
+import em_support as es
+from em_support import make_engine
+from helpers import need_gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -142,12 +142,12 @@ def _m_step_errors(c, eng, variant, Vb, V, got_of):
     """Per quantity the largest error over the utterances against the float64 formulas fed with the device's variances V,
     the bound it is held to, and what exceeds it."""
     err, bound, bad = {}, {}, []
-    for u, o in enumerate(_oracles_from(c, eng, variant, Vb, V)):
+    for u, o in enumerate(es.oracles_from(c, eng, variant, Vb, V)):
         with np.errstate(all="ignore"):
-            ref, o32 = _reference(o, variant)
+            ref, o32 = es.reference(o, variant)
         got = got_of(u)
-        e, b = _errors(got, ref), _bounds(_errors({k: o32[k] for k in got}, ref))
-        bad += [(u, k, e[k], b[k]) for k in _violations(e, b)]
+        e, b = es.errors(got, ref), es.bounds(es.errors({k: o32[k] for k in got}, ref))
+        bad += [(u, k, e[k], b[k]) for k in es.violations(e, b)]
         for k in e:
             if k not in err or not e[k] / b[k] <= err[k] / bound[k]:
                 err[k], bound[k] = e[k], b[k]
@@ -193,28 +193,28 @@ def _run(case):
         assert np.all(V[:, :, F:] == 0)
         r.decode = _logvar_errors(c, prec, c.Zs, V[:, :, :F], False)
         out = eng.wiener(R, want_masks=True)
-        m = _m_step_errors(c, eng, "M1", None, V[:, :, :F], lambda u: _device_wiener(c, eng, u, out))
-        r.dec_wiener = [_device_wiener(c, eng, u, out) for u in range(len(COUNTS))]
-        _padding_is_zero(eng, out[2], out[3], out[0].abs().sum(-1), out[1].abs().sum(-1))
+        m = _m_step_errors(c, eng, "M1", None, V[:, :, :F], lambda u: es.device_wiener(c, eng, u, out))
+        r.dec_wiener = [es.device_wiener(c, eng, u, out) for u in range(len(COUNTS))]
+        es.padding_is_zero(eng, out[2], out[3], out[0].abs().sum(-1), out[1].abs().sum(-1))
         with np.errstate(all="ignore"):                                    # (the references before the M-step moves the state)
-            refs = [_reference(o, "M1") for o in _oracles_from(c, eng, "M1", None, V[:, :, :F])]
+            refs = [es.reference(o, "M1") for o in es.oracles_from(c, eng, "M1", None, V[:, :, :F])]
         eng.m_step(R)
         cost = eng.cost_from_frames(R)
         mm = SimpleNamespace(err={}, bound={}, bad=[])
         for u, (ref, o32) in enumerate(refs):
-            got = _device_m_step(c, eng, u, cost, "M1")
-            e, b = _errors(got, ref), _bounds(_errors({k: o32[k] for k in got}, ref))
-            _merge(mm, SimpleNamespace(err=e, bound=b, bad=[(u, k, e[k], b[k]) for k in _violations(e, b)]))
+            got = es.device_m_step(c, eng, u, cost, "M1")
+            e, b = es.errors(got, ref), es.bounds(es.errors({k: o32[k] for k in got}, ref))
+            _merge(mm, SimpleNamespace(err=e, bound=b, bad=[(u, k, e[k], b[k]) for k in es.violations(e, b)]))
         r.decoding = _merge(m, mm)
         r.dec_state = states()
-        _padding_is_zero(eng)
+        es.padding_is_zero(eng)
         reset()
 
     # 2. the replayed chain, store on: log-acceptances, samples, stored rows
     eng.sample_store(True)
     eps = torch.from_numpy(_pad(c.eps, eng.Lp)).to(dev)
     acc = eng.mh_chain(c.ns, c.S_steps - c.ns, c.var_rw, eps=eps, u=torch.from_numpy(c.uu).to(dev), want_acc=True)
-    r.chain_kernel = _query(eng, "Q_CHAIN_KERNEL")
+    r.chain_kernel = es.query(eng, "Q_CHAIN_KERNEL")
     r.acc = acc.cpu().numpy().astype(np.float64)
     r.Zs = eng.Zs[:, :c.ns, :L].cpu().numpy().copy()
     r.Z = eng.Z[:, :L].cpu().numpy().copy()
@@ -226,29 +226,29 @@ def _run(case):
     # 3. a chain with the device generator and a burn-in; the stored M-step, cost and Wiener filter from its rows
     reset()
     eng.mh_chain(R, BURNIN, c.var_rw, call=1)
-    assert _query(eng, "Q_CHAIN_KERNEL") == r.chain_kernel
+    assert es.query(eng, "Q_CHAIN_KERNEL") == r.chain_kernel
     Zc = eng.Zs[:, :R, :L].cpu().numpy().copy()
     r.moved = float(np.abs(Zc - c.Z0[:, None, :]).max())
     rows = eng.stored_variances(R).cpu().numpy()
     r.rows_device = _logvar_errors(c, prec, Zc, rows[:, :, :F], prec == "bf16")
     V = rows[:, :, :F]
     out = eng.wiener_stored(want_masks=True)
-    m = _m_step_errors(c, eng, "M1", None, V, lambda u: _device_wiener(c, eng, u, out))
-    r.st_wiener = [_device_wiener(c, eng, u, out) for u in range(len(COUNTS))]
-    _padding_is_zero(eng, out[2], out[3], out[0].abs().sum(-1), out[1].abs().sum(-1))
+    m = _m_step_errors(c, eng, "M1", None, V, lambda u: es.device_wiener(c, eng, u, out))
+    r.st_wiener = [es.device_wiener(c, eng, u, out) for u in range(len(COUNTS))]
+    es.padding_is_zero(eng, out[2], out[3], out[0].abs().sum(-1), out[1].abs().sum(-1))
     with np.errstate(all="ignore"):
-        refs = [_reference(o, "M1") for o in _oracles_from(c, eng, "M1", None, V)]
+        refs = [es.reference(o, "M1") for o in es.oracles_from(c, eng, "M1", None, V)]
     eng.m_step_stored()
-    r.w_fused = _query(eng, "Q_W_FUSED")
+    r.w_fused = es.query(eng, "Q_W_FUSED")
     cost = eng.cost_from_frames(R)
     for u, (ref, o32) in enumerate(refs):
-        got = _device_m_step(c, eng, u, cost, "M1")
-        e, b = _errors(got, ref), _bounds(_errors({k: o32[k] for k in got}, ref))
-        _merge(m, SimpleNamespace(err=e, bound=b, bad=[(u, k, e[k], b[k]) for k in _violations(e, b)]))
+        got = es.device_m_step(c, eng, u, cost, "M1")
+        e, b = es.errors(got, ref), es.bounds(es.errors({k: o32[k] for k in got}, ref))
+        _merge(m, SimpleNamespace(err=e, bound=b, bad=[(u, k, e[k], b[k]) for k in es.violations(e, b)]))
     r.stored = m
     r.st_state = states()
     r.st_samples = Zc
-    _padding_is_zero(eng)
+    es.padding_is_zero(eng)
 
     # 4. the gains-only M-step with a fixed noise PSD, from the same rows
     Vb = _noise_psd(c)
@@ -257,14 +257,14 @@ def _run(case):
     eng.set_noise_psd(Vbp.to(dev))
     eng.g.copy_(torch.from_numpy(c.gains))
     with np.errstate(all="ignore"):
-        refs = [_reference(o, "noNMF") for o in _oracles_from(c, eng, "noNMF", Vb, V)]
+        refs = [es.reference(o, "noNMF") for o in es.oracles_from(c, eng, "noNMF", Vb, V)]
     eng.m_step_stored()
     cost = eng.cost_from_frames(R)
     g = SimpleNamespace(err={}, bound={}, bad=[])
     for u, (ref, o32) in enumerate(refs):
-        got = _device_m_step(c, eng, u, cost, "noNMF")
-        e, b = _errors(got, {k: ref[k] for k in got}), _bounds(_errors({k: o32[k] for k in got}, ref))
-        _merge(g, SimpleNamespace(err=e, bound=b, bad=[(u, k, e[k], b[k]) for k in _violations(e, b)]))
+        got = es.device_m_step(c, eng, u, cost, "noNMF")
+        e, b = es.errors(got, {k: ref[k] for k in got}), es.bounds(es.errors({k: o32[k] for k in got}, ref))
+        _merge(g, SimpleNamespace(err=e, bound=b, bad=[(u, k, e[k], b[k]) for k in es.violations(e, b)]))
     r.gains_only = g
     eng.set_noise_psd(None)
     eng.sample_store(False)
@@ -382,7 +382,7 @@ def test_results_do_not_depend_on_the_amplitude(case):
         sl = slice(off[u], off[u + 1])
         ga = dict(wa[u], W=sa["W"][u, :F, :K], H=sa["Ht"][sl, :K].T, g=sa["g"][sl])
         gb = dict(wb[u], W=sb["W"][u, :F, :K], H=sb["Ht"][sl, :K].T, g=sb["g"][sl])
-        e = _errors(_scaled_back(ga, ca.amp), {k: np.asarray(v, np.complex128 if np.iscomplexobj(v) else np.float64) for k, v in gb.items()})
+        e = es.errors(_scaled_back(ga, ca.amp), {k: np.asarray(v, np.complex128 if np.iscomplexobj(v) else np.float64) for k, v in gb.items()})
         for k in e:
             worst[k] = max(worst.get(k, 0.0), e[k] / (ba[k] + bb[k]))
     print("VALUE %s scale: against amplitude 1, over the sum of the two bounds: " % vc.case_id(case) + " ".join("%s %.3f" % kv for kv in worst.items()))
@@ -430,7 +430,7 @@ def test_a_degenerate_utterance_does_not_reach_its_neighbours(shape, prec):
             with np.errstate(all="ignore"):
                 cost, S, N = eng.run(niter, nsE, biE, nsW, biW, c.var_rw)
             outs.append(SimpleNamespace(eng=eng, cost=cost.cpu().numpy(), S=S.cpu().numpy(), N=N.cpu().numpy(), W=eng.W.cpu().numpy().copy(),
-                                        Ht=eng.Ht.cpu().numpy().copy(), g=eng.g.cpu().numpy().copy(), graph=_query(eng, "Q_EM_GRAPH")))
+                                        Ht=eng.Ht.cpu().numpy().copy(), g=eng.g.cpu().numpy().copy(), graph=es.query(eng, "Q_EM_GRAPH")))
         assert [o.graph for o in outs] == [0, 1, 1]
         return outs
 

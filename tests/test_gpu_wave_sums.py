@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_parity import need_gpu
+from helpers import need_gpu
 
 pytestmark = pytest.mark.gpu
 

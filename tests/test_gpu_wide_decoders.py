@@ -9,7 +9,7 @@ Tolerances are those tests/test_gpu_parity.py uses for the same quantities on m1
 absolute, decisions equal, Zs 5e-6, Z 1e-5, Vs 2e-4; after the first M-step W / H / g / Vb 5e-4 and the cost 1e-4; after the
 full run cost 2e-4, S_hat / N_hat 2e-3 (L2), WFs 5e-3, W / g 2e-3.  bf16 mode: Vs 5e-2.  Trajectories on recorded numpy
 draws are compared frame by frame up to the first decision the ORACLE itself makes closer than 5e-4 to its threshold
-(wide_cases.first_narrow); at most 15 % of a case's frames may be cut short that way, and
+(em_support.first_narrow); at most 15 % of a case's frames may be cut short that way, and
 tests/test_wide_decoders_cpu.py checks on the CPU that the chosen seeds stay under that cap.
 """
 import ctypes as C
@@ -21,63 +21,19 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import vaenmf_oracle as orc
-from helpers import rel_err, nrm_err
-from wide_cases import (WIDE_CASES, load_wide_case, make_engine, enc_list, dec_list, sweep_case, SWEEP, SWEEP_COUNTS, RAGGED,
-                        cut_short, make_X, RecordingRNG, first_narrow)
-
-
-def need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-
-
-def query(eng, what):
-    from vaenmf import _lib
-    return _lib.lib().vaenmf_plan_query(eng._plan, what)
-
-
-def to_c(t, N, F):
-    return np.ascontiguousarray(t[:, :F].cpu().numpy()).view(np.complex64).reshape(N, F).T
+from em_support import RecordingRNG, dec_list, enc_list, first_narrow, make_engine, query, replay_buffers, setup_from_case, to_c
+from helpers import need_gpu, rel_err, nrm_err
+from wide_cases import WIDE_CASES, load_wide_case, sweep_case, SWEEP, SWEEP_COUNTS, RAGGED, cut_short, make_X
 
 
 # ------------------------------------------------------------------------------------------------------------------
 # 1. reference trajectories
 # ------------------------------------------------------------------------------------------------------------------
-def setup_from_case(name, model):
-    z, params, draws, meta = load_wide_case(name)
-    nsE, biE, nsW, biW = meta["counts"]
-    o = orc.MCEMOracle(model, meta["niter"], nsE, biE, nsW, biW, 0.01, reference_compat=True)
-    rng = orc.ReplayRNG(draws)
-    y = z["y"] if model == "M2" else None
-    o.init_parameters(z["X"], params, meta["K"], 1e-8, rng, y=y)
-    ns, bi = o.e_step_counts()
-    nw, bw = o.wf_counts()
-    eng = make_engine(params, meta["F"], meta["K"], [meta["N"]], Rcap=max(ns, nw))
-    assert eng.wide and eng.Lp == 128 and eng.Z.shape[1] == 128
-    eng.set_spectrogram([z["X"]])
-    eng.init_nmf([z["W0"]], [z["H0"]])
-    if y is not None:
-        eng.set_labels(torch.from_numpy(y))
-    eng.Z.zero_()
-    eng.Z[:, :meta["L"]].copy_(torch.from_numpy(np.ascontiguousarray(z["Z0"].T)))
-    return z, params, meta, o, rng, eng
-
-
-def replay_buffers(rng, S, N, Lp, dev):
-    """The next S (randn(L,N), rand(N)) pairs of the recorded stream in the engine's layout [S][N][Lp]."""
-    eps = np.zeros((S, N, Lp), np.float32)
-    u = np.empty((S, N), np.float32)
-    for m in range(S):
-        eps[m, :, :rng.draws[rng.pos].shape[0]] = rng.draws[rng.pos].T
-        u[m] = rng.draws[rng.pos + 1]
-        rng.pos += 2
-    return torch.from_numpy(eps).to(dev), torch.from_numpy(u).to(dev)
-
-
 @pytest.mark.parametrize("name,model", WIDE_CASES)
 def test_encoder_init(name, model):
     need_gpu()
-    z, params, meta, o, rng, eng = setup_from_case(name, model)
+    z, params, meta, o, rng, eng = setup_from_case(name, model, load=load_wide_case)
+    assert eng.wide and eng.Lp == 128 and eng.Z.shape[1] == 128
     y = torch.from_numpy(z["y"]).to(eng.device) if model == "M2" else None
     eng.encode(enc_list(params), y)
     L = meta["L"]
@@ -90,7 +46,8 @@ def test_first_em_iteration(name, model):
     """E-step chain (every log-acceptance of every frame, every decision, the samples, the store's variances), then the
     M-step, against the reference's recorded first iteration."""
     need_gpu()
-    z, params, meta, o, rng, eng = setup_from_case(name, model)
+    z, params, meta, o, rng, eng = setup_from_case(name, model, load=load_wide_case)
+    assert eng.wide and eng.Lp == 128 and eng.Z.shape[1] == 128
     ns, bi = o.e_step_counts()
     S, N, F, K, L = ns + bi, meta["N"], meta["F"], meta["K"], meta["L"]
     pos0 = rng.pos
@@ -123,7 +80,8 @@ def test_first_em_iteration(name, model):
 @pytest.mark.parametrize("name,model", WIDE_CASES)
 def test_full_run_replay(name, model):
     need_gpu()
-    z, params, meta, o, rng, eng = setup_from_case(name, model)
+    z, params, meta, o, rng, eng = setup_from_case(name, model, load=load_wide_case)
+    assert eng.wide and eng.Lp == 128 and eng.Z.shape[1] == 128
     ns, bi = o.e_step_counts()
     nw, bw = o.wf_counts()
     N, F = meta["N"], meta["F"]

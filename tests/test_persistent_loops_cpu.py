@@ -1,6 +1,6 @@
 """No GPU: the cases of tests/test_gpu_persistent_loops.py reach what they are for.
 
-wave_frames / chain_rounds / decode_trips (tests/test_gpu_bin_counts.py, next to shape_class) restate which frames, wave
+wave_frames / chain_rounds / decode_trips (tests/dispatch_model.py, next to shape_class) restate which frames, wave
 tiles and tiles a wavefront or workgroup of the persistent kernels walks, trip by trip, for a grid capped by
 VAENMF_GRID_CAP.  The assertions below are about the capped cases of the GPU module: if a batch, a cap or the dispatch
 changes so that a case stops reaching a second trip, an utterance boundary inside a block, a clipped block, an empty
@@ -8,12 +8,11 @@ wavefront, ..., this test fails instead of the GPU module silently testing less.
 """
 import numpy as np
 
-from test_gpu_bin_counts import (COUNTS, N_WAVE_TILES, chain_grid, chain_rounds, chain_waves, decode_grid, decode_tiles, decode_trips,
-                                 shape_class, stream_grid, wave_frames, wave_tiles)
-from test_gpu_persistent_loops import (CHAIN_CASES, CHAIN_COUNTS, CHAIN_FORMS, CHAIN_K, CHAIN_R, MAX_LEFT_OUT, STREAM_CAPS, STREAM_CASES,
-                                       TILE_CAPS, TILE_CASES, _chain_reference, chain_form, default_chain_counts,
-                                       default_stream_counts)
-from test_gpu_rank_and_samples import decode_class, stream_class
+from dispatch_model import (COUNTS, N_WAVE_TILES, chain_form, chain_grid, chain_rounds, chain_waves, decode_class, decode_grid, decode_tiles,
+                            decode_trips, default_chain_counts, default_stream_counts, shape_class, stream_class, stream_grid, wave_frames,
+                            wave_tiles)
+from persistent_cases import (CHAIN_CASES, CHAIN_COUNTS, CHAIN_FORMS, CHAIN_K, CHAIN_R, MAX_LEFT_OUT, STREAM_CAPS, STREAM_CASES, TILE_CAPS,
+                              TILE_CASES, chain_reference)
 
 N_CUS = 256
 
@@ -150,7 +149,7 @@ def test_chain_oracle_leaves_out_at_most_15_percent():
     """The decision-margin rule of the chain sweeps (a frame counts when each of its decisions is 1e-2 from the threshold)
     on the oracle's own trace: the inputs' seeds (CHAIN_SEEDS) keep the share of frames it leaves out within 15 %."""
     for F, labels in sorted({(F, labels) for F, p, labels in CHAIN_CASES if p == "bf16x3"}):
-        refs, left_out = _chain_reference(F, labels)
+        refs, left_out = chain_reference(F, labels)
         print("chain F=%d labels=%d: %.1f %% of %d frames left out" % (F, labels, 100 * left_out, sum(CHAIN_COUNTS)))
         assert left_out <= MAX_LEFT_OUT, (F, labels, left_out)
         assert all(r.keep.any() for r in refs if len(r.keep) > 4)

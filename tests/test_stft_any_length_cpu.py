@@ -1,68 +1,12 @@
 """Any-length STFT / iSTFT, host side (no GPU): frame geometry for every n_fft in [16, 4096], center on and off, the
 rejections, and the numpy float64 restatement of librosa's stft / istft that the GPU tests measure against.  The
 restatement is anchored here to the oracle, which is pinned to the reference's own committed spectrograms."""
-import math
-
 import numpy as np
 import pytest
 
 import vaenmf_oracle as orc
 from helpers import GOLDEN
-
-TINY = np.finfo(np.float32).tiny
-
-
-def ref_window(win, nfft):
-    """librosa.filters.get_window(win, nfft, fftbins=True)."""
-    if isinstance(win, (str, tuple)):
-        from scipy.signal import get_window
-        return get_window(win, nfft, fftbins=True)
-    w = np.asarray(win, dtype=np.float64)
-    assert w.shape == (nfft,)
-    return w
-
-
-def ref_geometry(T, fs, wlen_sec, hop_percent, center=True):
-    """(nfft, hop, end-padded length, n_frames): stft.py:37-53, then librosa's frame count."""
-    nfft = int(wlen_sec * fs)
-    hop = int(hop_percent * nfft)
-    utt_len = T / fs
-    Tp = T + (hop if math.ceil(utt_len / wlen_sec / hop_percent) != int(utt_len / wlen_sec / hop_percent) else 0)
-    L = Tp + 2 * (nfft // 2) if center else Tp
-    return nfft, hop, Tp, 1 + (L - nfft) // hop
-
-
-def ref_stft(x, fs=16000, wlen_sec=50e-3, win="hann", hop_percent=0.25, center=True, pad_mode="reflect"):
-    """stft.py:16-63 -> librosa.core.stft in float64: end pad, np.pad by n_fft//2 in `pad_mode` when centred,
-    frames at hop, window, rfft.  Returns complex128 (n_fft//2+1, n_frames)."""
-    nfft, hop, Tp, nfr = ref_geometry(len(x), fs, wlen_sec, hop_percent, center)
-    y = np.pad(np.asarray(x, dtype=np.float64), (0, Tp - len(x)), mode="constant")
-    if center:
-        y = np.pad(y, nfft // 2, mode=pad_mode)
-    idx = np.arange(nfft)[None, :] + hop * np.arange(nfr)[:, None]
-    return np.fft.rfft(y[idx] * ref_window(win, nfft)[None, :], axis=1).T
-
-
-def ref_istft(S, fs=16000, wlen_sec=50e-3, win="hann", hop_percent=0.25, center=True, max_len=None):
-    """stft.py:66-102 -> librosa.core.istft in float64: irfft, synthesis window, overlap-add, division by the window's
-    sum of squares where it exceeds float32's tiny, n_fft//2 trimmed when centred, fixed to max_len."""
-    nfft = int(wlen_sec * fs)
-    hop = int(hop_percent * nfft)
-    nfr = S.shape[1]
-    w = ref_window(win, nfft)
-    frames = np.fft.irfft(np.asarray(S).T, n=nfft, axis=1) * w[None, :]
-    n_out = nfft + hop * (nfr - 1)
-    y, wss = np.zeros(n_out), np.zeros(n_out)
-    for i in range(nfr):
-        y[i * hop:i * hop + nfft] += frames[i]
-        wss[i * hop:i * hop + nfft] += w * w
-    nz = wss > TINY
-    y[nz] /= wss[nz]
-    start = nfft // 2 if center else 0
-    if max_len is None:
-        return y[start:n_out - start]
-    y = y[start:start + max_len]
-    return np.pad(y, (0, max_len - len(y)))
+from stft_cases import ref_geometry, ref_istft, ref_stft
 
 
 def _speech():

@@ -22,6 +22,7 @@ from types import SimpleNamespace
 import numpy as np
 
 import vaenmf_oracle as orc
+from em_support import gains_step64
 
 COUNTS = [21, 40, 9]
 # level -> (scales of decoder.hidden.0 / .hidden.1 / .reconstruction, variance of the random walk)
@@ -257,7 +258,6 @@ def pair_products(c):
         take(q[:, :, 0] * q[:, :, 2], q[:, :, 1] * q[:, :, 3], x[:, :, 0] * q[:, :, 2], x[:, :, 2] * q[:, :, 0],
              x[:, :, 1] * q[:, :, 3], x[:, :, 3] * q[:, :, 1], Vx * Vx)
     Vs = np.exp(decoder64(c.params, _zin_rows(c, c.Zs))[0]).reshape(c.NT, c.R, c.F)
-    from test_gpu_rank_and_samples import gains_step64
     for u in range(len(COUNTS)):
         sl = slice(c.off[u], c.off[u + 1])
         V = np.moveaxis(Vs[sl], 0, -1)                                       # (R, F, n)

@@ -6,6 +6,7 @@ import hashlib
 import numpy as np
 
 import vaenmf_oracle as orc
+from em_support import oracle_iteration
 from helpers import load_case
 
 # name, model; the reference's h_dim (the decoder runs over reversed(h_dim), models.py:133)
@@ -35,78 +36,9 @@ def load_wide_case(name):
     return _cache[name]
 
 
-# ---------------------------------------------------------------------------------------------------------------
-# engines and oracle runs shared by tests/test_gpu_wide_decoders.py (and the CPU check of the sweep's seeds)
-# ---------------------------------------------------------------------------------------------------------------
-def dec_list(params):
-    keys = ["decoder.hidden.%d.%s" % (i, k) for i in range(orc.n_hidden(params, "decoder")) for k in ("weight", "bias")]
-    return [params[k] for k in keys + ["decoder.reconstruction.weight", "decoder.reconstruction.bias"]]
-
-
-def enc_list(params):
-    enc = [(params["encoder.hidden.%d.weight" % i], params["encoder.hidden.%d.bias" % i]) for i in range(orc.n_hidden(params, "encoder"))]
-    return enc + [(params["encoder.sample.mu.weight"], params["encoder.sample.mu.bias"])]
-
-
-def make_engine(params, F, K, counts, Rcap, precision="bf16x3", seeds=None):
-    from vaenmf.engine import BatchEngine
-    eng = BatchEngine(F, K, dec_list(params), precision=precision, max_frames=sum(counts), max_utts=len(counts),
-                      z_dim=int(params["encoder.sample.mu.weight"].shape[0]))
-    return eng.bind(counts, Rcap=Rcap, seeds=seeds)
-
-
-class RecordingRNG:
-    """Seeded numpy generator (the oracle's NumpyRNG) that keeps what it drew, in order."""
-
-    def __init__(self, seed):
-        self.g, self.draws = orc.NumpyRNG(seed), []
-
-    def rand(self, *shape):
-        self.draws.append(self.g.rand(*shape))
-        return self.draws[-1]
-
-    def randn(self, *shape):
-        self.draws.append(self.g.randn(*shape))
-        return self.draws[-1]
-
-
-MIN_MARGIN = 5e-4      # a replayed decision is comparable when the oracle's own margin |log u - acc| is at least this
-
-
-def first_narrow(draws, acc):
-    """Per frame: the first step whose decision sits closer than MIN_MARGIN to its threshold (the number of steps: none)."""
-    u = np.stack([draws[2 * m + 1] for m in range(acc.shape[0])])
-    narrow = np.abs(np.log(u) - acc) < MIN_MARGIN
-    return np.where(narrow.any(0), narrow.argmax(0), acc.shape[0])
-
-
 def make_X(n, F, g):
     return ((g.standard_normal((n, F)) + 1j * g.standard_normal((n, F))) * (0.5 + 3 * np.exp(-np.arange(F) / (F / 6.0 + 1.0)))
             * np.exp(0.5 * g.standard_normal((n, 1)))).astype(np.complex64)
-
-
-def oracle_iteration(model, X, params, K, seed, counts, y=None):
-    """One EM iteration and the Wiener chain of the oracle for one utterance on a recorded numpy stream."""
-    nsE, biE, nsW, biW = counts
-    o = orc.MCEMOracle(model, 1, nsE, biE, nsW, biW, 0.01, reference_compat=False)
-    r = RecordingRNG(seed)
-    o.init_parameters(X, params, K, 1e-8, r, y=y)
-    out = dict(o=o, W0=o.W.copy(), H0=o.H.copy(), Z0=o.Z.copy())
-    tr, p0 = [], len(r.draws)
-    Zs = o.sample_posterior(o.Z, nsE, biE, trace=tr)
-    out["e_draws"], out["acc"], out["Zs"] = r.draws[p0:], np.stack([t["acc"] for t in tr]), Zs
-    o.Z = Zs[:, -1, :].T.copy()
-    o.compute_Vs(Zs); o.compute_Vs_scaled(); o.compute_Vx()
-    out["Vs"] = o.Vs.copy()
-    o.M_step()
-    out["W"], out["H"], out["g"], out["cost"] = o.W.copy(), o.H.copy(), o.g.copy(), float(o.compute_expected_neg_log_like())
-    tr2, p1 = [], len(r.draws)
-    Zw = o.sample_posterior(o.Z, nsW, biW, trace=tr2)
-    out["w_draws"], out["w_acc"] = r.draws[p1:], np.stack([t["acc"] for t in tr2])
-    o.compute_Vs(Zw); o.compute_Vs_scaled(); o.compute_Vx()
-    out["WFs"], out["WFn"] = o.compute_WF(sample=False)
-    out["e_cut"], out["w_cut"] = first_narrow(out["e_draws"], out["acc"]), first_narrow(out["w_draws"], out["w_acc"])
-    return out
 
 
 # The shape and edge sweep: (F, z_dim, the reference's h_dim, frame counts, K, model).  F = 1, 17, 65, 130, 257, 640 are 1, 2, 5, 9,
