@@ -403,9 +403,17 @@ def decode_inputs(F, z_dim, Dy, Lp=32):
     return SimpleNamespace(Zs=Zs, y=y, pos=frame_positions(COUNTS))
 
 
+# (F, z_dim, Dy) -> further words of the generator seed of a chain case's inputs.  A 168-row case resolves a share of
+# differing elements to 4e-4 per tile: where the emulation's floor at the plain seed is two or three such elements instead of
+# one, a used statistic falls short of SEPARATION floors below its ceiling (tile_share 75 floors at (513, 16, 0), share 53 at
+# (257, 16, 1)), which tests/test_bf16_model_cpu.py refuses.  Such a case gets other inputs, chosen on the CPU from the
+# emulation alone; no bound moves.
+CHAIN_INPUT_SALT = {(513, 16, 0): [1], (257, 16, 1): [3]}
+
+
 def chain_inputs(F, z_dim, Dy, Lp=32):
     """A state of the engine and the replayed noise of one chain of CHAIN_BURNIN + CHAIN_NS steps."""
-    g = np.random.default_rng([F, z_dim, Dy, 2])
+    g = np.random.default_rng([F, z_dim, Dy, 2] + CHAIN_INPUT_SALT.get((F, z_dim, Dy), []))
     NT, S, K = sum(COUNTS), CHAIN_NS + CHAIN_BURNIN, RANK
     c = SimpleNamespace(ns=CHAIN_NS, burnin=CHAIN_BURNIN, var_rw=VAR_RW, pos=frame_positions(COUNTS))
     c.Xs = [((g.standard_normal((n, F)) + 1j * g.standard_normal((n, F))) * (0.5 + 3 * np.exp(-np.arange(F) / 60.0))).astype(np.complex64) for n in COUNTS]
@@ -431,7 +439,9 @@ DECODE_CASES = [("f65", 65, 32, (128, 128), 0),                # 5 bin tiles, ex
                 ("f513", 513, 32, (128, 128), 0),
                 ("f65_z16", 65, 16, (128, 128), 0),
                 ("f65_h128", 65, 32, (128,), 0),
-                ("f257_labels", 257, 32, (128, 128), 1)]
+                ("f257_labels", 257, 32, (128, 128), 1),
+                ("f257_z16_h128", 257, 16, (128,), 0),         # geometry 3, the one-hidden branch of Dec::hidden with its own odd-bin dot
+                ("f513_z16_h128", 513, 16, (128,), 0)]         # geometry 4, the reference's bin count
 # id, F, z_dim, h_dim, label width, kernel switches, VAENMF_Q_CHAIN_KERNEL, the model's switches
 _WAVE = {"b1_bf16": False, "last_bin_fp32": False}
 CHAIN_CASES = [("wave8_f257", 257, 32, (128, 128), 0, {"VAENMF_WCHAIN4": "0"}, 1, _WAVE),
@@ -443,7 +453,25 @@ CHAIN_CASES = [("wave8_f257", 257, 32, (128, 128), 0, {"VAENMF_WCHAIN4": "0"}, 1
                ("wave4_f513", 513, 32, (128, 128), 0, {}, 2, _WAVE),
                ("wave4_f257_labels", 257, 32, (128, 128), 1, {}, 2, {"b1_bf16": True, "last_bin_fp32": False}),
                ("team_f257", 257, 32, (128, 128), 0, {"VAENMF_TEAM_CHAIN": "1"}, 0, {"b1_bf16": False, "last_bin_fp32": True}),
-               ("wide_f130", 130, 128, (256, 128), 0, {}, 3, _WAVE)]
+               ("wide_f130", 130, 128, (256, 128), 0, {}, 3, _WAVE),
+               # the narrow decoders beside 32 / [128, 128]: one hidden layer (the wave kernels copy layer 1's fragments, the team
+               # kernel takes Dec::hidden's one-hidden branch) and z_dim 16 (sd_hi = 0 in the wave kernels, the noise mask per
+               # latent quad in the team kernel, which takes the layer-1 bias rows of the labels in float32)
+               ("wave4_f257_z16_h128", 257, 16, (128,), 0, {}, 2, _WAVE),
+               ("wave_f513_z16_h128", 513, 16, (128,), 0, {"VAENMF_WCHAIN4": "0"}, 1, _WAVE),
+               ("team_f257_h128", 257, 32, (128,), 0, {"VAENMF_TEAM_CHAIN": "1"}, 0, {"b1_bf16": False, "last_bin_fp32": True}),
+               ("team_f257_z16_labels", 257, 16, (128, 128), 1, {"VAENMF_TEAM_CHAIN": "1"}, 0, {"b1_bf16": False, "last_bin_fp32": True})]
+
+
+# cases added after the first lists: tests parametrised over the SET of shapes put theirs behind the earlier ones, so that
+# the ids pytest numbers (h_dim0 ..) stay what they were
+LATER_CASES = ("f257_z16_h128", "f513_z16_h128", "wave4_f257_z16_h128", "wave_f513_z16_h128", "team_f257_h128", "team_f257_z16_labels")
+
+
+def case_shapes():
+    """(F, z_dim, h_dim, Dy) of every case, without repeats: the earlier cases' shapes sorted, then the later ones' sorted."""
+    of = lambda later: {c[1:5] for c in DECODE_CASES + CHAIN_CASES if (c[0] in LATER_CASES) == later}
+    return sorted(of(False)) + sorted(of(True) - of(False))
 
 
 def latent_columns(z_dim, h_dim):

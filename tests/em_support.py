@@ -5,6 +5,7 @@ library are loaded inside the functions that use them.
 The module is not a test module, so pytest does not rewrite its asserts: each one carries its own message with the
 compared values."""
 import contextlib
+import hashlib
 import os
 from types import SimpleNamespace
 
@@ -172,17 +173,24 @@ def replay_tensors(outs, key, S, dev):
 # ---------------------------------------------------------------------------------------------------------------------
 # the sweeps over F, K and R: one recipe of inputs, the oracle in the engine's state, comparisons at stated tolerances
 # generator seed of a case's inputs when it is not 1000 + F (a case whose oracle margins leave out more than 15 % of the frames)
-INPUT_SEEDS = {}
+# key: (F, K, R) at the default decoder shape, (F, K, R, z_dim, h_dim, Dy) at any other.  (17, 10, 10) at 32 / [128]: 17.1 %
+# at seed 1017, 8.6 % at the first seed tried after it.
+INPUT_SEEDS = {(17, 10, 10, 32, (128,), 0): 2017}
 
 
-def inputs(F, K, R, Dy=0, counts=None, seed=None):
+def inputs(F, K, R, Dy=0, counts=None, seed=None, z_dim=32, h_dim=(128, 128)):
     """The recipe of test_m_step_and_chain_other_shapes: ragged batch, tilted spectrogram, Xavier decoder.  counts: the
-    frames per utterance (COUNTS); seed: the generator seed of the inputs (INPUT_SEEDS, else 1000 + F)."""
-    params = orc.xavier_normal_params([F, 32, [128, 128]], seed=7, y_dim=Dy, bias_std=0.05)
-    g = np.random.default_rng(INPUT_SEEDS.get((F, K, R), 1000 + F) if seed is None else seed)
+    frames per utterance (COUNTS); seed: the generator seed of the inputs (INPUT_SEEDS, else 1000 + F).  z_dim, h_dim: the
+    decoder's shape as the reference names it.  Every array is drawn at 32 latent columns in one generator order, whatever
+    z_dim is, and the columns z_dim..31 of Zs, eps and Z0 (the engine's zero padding) are cleared afterwards: the defaults
+    give the bytes they always gave (tests/test_decoder_shapes_cpu.py holds their hash)."""
+    h_dim = tuple(h_dim)
+    params = orc.xavier_normal_params([F, z_dim, list(h_dim)], seed=7, y_dim=Dy, bias_std=0.05)
+    key = (F, K, R) if (z_dim, h_dim) == (32, (128, 128)) else (F, K, R, z_dim, h_dim, Dy)
+    g = np.random.default_rng(INPUT_SEEDS.get(key, 1000 + F) if seed is None else seed)
     counts = list(COUNTS if counts is None else counts)
     NT = sum(counts)
-    c = SimpleNamespace(F=F, K=K, R=R, Dy=Dy, params=params, NT=NT, S_steps=6, ns=3, counts=counts)
+    c = SimpleNamespace(F=F, K=K, R=R, Dy=Dy, params=params, NT=NT, S_steps=6, ns=3, counts=counts, L=int(z_dim), Lp=32, h_dim=h_dim)
     c.Xs = [((g.standard_normal((n, F)) + 1j * g.standard_normal((n, F))) * (0.5 + 3 * np.exp(-np.arange(F) / 60.0))).astype(np.complex64) for n in counts]
     c.W0 = [np.maximum(g.random((F, K)), 1e-8).astype(np.float32) for _ in counts]
     c.H0 = [np.maximum(g.random((K, n)), 1e-8).astype(np.float32) for n in counts]
@@ -192,12 +200,29 @@ def inputs(F, K, R, Dy=0, counts=None, seed=None):
     c.eps = g.standard_normal((c.S_steps, NT, 32)).astype(np.float32)
     c.uu = g.random((c.S_steps, NT)).astype(np.float32)
     c.Z0 = (0.5 * g.standard_normal((NT, 32))).astype(np.float32)
+    for a in (c.Zs, c.eps, c.Z0):
+        a[..., c.L:] = 0
     c.off = np.concatenate([[0], np.cumsum(counts)])
     return c
 
 
+def digest(c):
+    """sha256 over everything inputs() returned, in a fixed order."""
+    h = hashlib.sha256()
+    for k in sorted(c.params):
+        h.update(k.encode()); h.update(np.ascontiguousarray(c.params[k]).tobytes())
+    for name in ("Xs", "W0", "H0", "ys"):
+        for a in getattr(c, name):
+            h.update(name.encode()); h.update(b"-" if a is None else np.ascontiguousarray(a).tobytes())
+    for name in ("Zs", "gains", "eps", "uu", "Z0", "off"):
+        h.update(name.encode()); h.update(np.ascontiguousarray(getattr(c, name)).tobytes())
+    h.update(repr((c.F, c.K, c.R, c.Dy, c.NT, c.S_steps, c.ns, c.counts)).encode())
+    return h.hexdigest()
+
+
 def engine(c, precision, Rcap=None, seeds=None):
     eng = make_engine(c.params, c.F, c.K, c.counts, Rcap=Rcap or c.R, precision=precision, seeds=seeds)
+    assert (eng.L, eng.Lp, eng.H2) == (c.L, c.Lp, 128 if len(c.h_dim) == 2 else 0), "engine of another decoder shape: %s" % ((eng.L, eng.Lp, eng.H2),)
     eng.set_spectrogram(c.Xs)
     eng.init_nmf(c.W0, c.H0)
     if c.Dy:
@@ -206,15 +231,24 @@ def engine(c, precision, Rcap=None, seeds=None):
     return eng
 
 
+def decoder_of(c, Zs):
+    """orc.decoder_forward of the samples Zs [NT, R, 32] (the first z_dim columns, and the labels where the case has them): [NT, R, F]."""
+    zin = Zs[..., :c.L]
+    if c.Dy:
+        zin = np.concatenate([zin, np.broadcast_to(np.concatenate(c.ys)[:, None, :], zin.shape[:2] + (c.Dy,))], 2)
+    return orc.decoder_forward(c.params, zin.reshape(-1, zin.shape[2])).reshape(zin.shape[0], zin.shape[1], c.F)
+
+
 def oracle_at(c, eng, u, Zs=None):
-    """The oracle of utterance u in the engine's present state (W, H, g), with the variances of the samples Zs."""
+    """The oracle of utterance u in the engine's present state (W, H, g), with the variances of the samples Zs (of which
+    the oracle gets the first z_dim columns)."""
     sl = eng.utt_slice(u)
     o = orc.MCEMOracle("M2" if c.Dy else "M1", 1)
     o.init_parameters(c.Xs[u], c.params, c.K, 1e-8, orc.NumpyRNG(0), y=c.ys[u], W0=eng.W[u, :c.F, :c.K].cpu().numpy(),
                       H0=eng.Ht[sl, :c.K].cpu().numpy().T.copy())
     o.g = eng.g[sl].cpu().numpy().copy()
     if Zs is not None:
-        o.compute_Vs(Zs[sl]); o.compute_Vs_scaled(); o.compute_Vx()
+        o.compute_Vs(Zs[sl][..., :c.L]); o.compute_Vs_scaled(); o.compute_Vx()
     return o
 
 
@@ -268,6 +302,255 @@ def wiener_against(c, eng, oracles, out, tol, tag, absolute=False):
         print("%s F=%d K=%d utt %d: Wiener " % (tag, F, c.K, u) + " ".join("%.2e" % v for v in e))
         assert max(e) < tol, (tag, u, e, "bound", tol)
     padding_is_zero(eng, WFs, WFn, S.abs().sum(-1), Nn.abs().sum(-1))
+
+
+def n_wave_tiles(c):
+    return sum((n + 15) // 16 for n in c.counts)
+
+
+LEFT_OUT_CAP = 0.15      # the share of frames a replayed chain may leave out of the comparison of its samples
+KEEP_MARGIN = 1e-2       # ... a frame is left out when one of its decisions sits closer than this to its threshold
+
+
+def chain_references(c, state_of):
+    """The oracle's replayed chain of c.S_steps steps per utterance on the case's draws (their first z_dim columns), from
+    the oracle state_of(u) gives: [(frames, log-acceptances, samples, frames whose every decision is clear)]."""
+    refs = []
+    for u in range(len(c.counts)):
+        sl = slice(int(c.off[u]), int(c.off[u + 1]))
+        o = state_of(u)
+        draws = []
+        for m in range(c.S_steps):
+            draws += [c.eps[m, sl, :c.L].T.copy(), c.uu[m, sl].copy()]
+        o.rng = orc.ReplayRNG(draws)
+        tr = []
+        Zs_ref = o.sample_posterior(c.Z0[sl, :c.L].T.copy(), c.ns, c.S_steps - c.ns, trace=tr)
+        ref_acc = np.stack([t["acc"] for t in tr])
+        keep = np.abs(np.log(c.uu[:, sl]) - ref_acc).min(0) > KEEP_MARGIN       # decisions are only comparable away from the threshold
+        refs.append((sl, ref_acc, Zs_ref, keep))
+    return refs
+
+
+def left_out(refs):
+    return 1.0 - np.concatenate([r[3] for r in refs]).mean()
+
+
+def initial_oracle(c, u):
+    """The oracle of utterance u in the state inputs() describes (W0, H0, gains), before any device call."""
+    sl = slice(int(c.off[u]), int(c.off[u + 1]))
+    o = orc.MCEMOracle("M2" if c.Dy else "M1", 1)
+    o.init_parameters(c.Xs[u], c.params, c.K, 1e-8, orc.NumpyRNG(0), y=c.ys[u], W0=c.W0[u], H0=c.H0[u])
+    o.g = c.gains[sl].copy()
+    return o
+
+
+def cpu_left_out(c, after_m_step):
+    """The share of frames the oracle's own margins leave out of a case's replayed chain, from the CPU alone.
+    after_m_step: the chain starts where split_mode_case starts it, after one M-step over the given samples c.Zs (the
+    oracle's own here; the engine's state is within 1e-3 of it); else from the state of inputs(), as bench_mode_case does."""
+    def state(u):
+        o = initial_oracle(c, u)
+        if after_m_step:
+            sl = slice(int(c.off[u]), int(c.off[u + 1]))
+            o.compute_Vs(c.Zs[sl][..., :c.L]); o.compute_Vs_scaled(); o.compute_Vx()
+            o.M_step()
+        return o
+    return left_out(chain_references(c, state))
+
+
+def split_mode_case(c):
+    """bf16x3 mode at one case of inputs(): decoding kernel, Wiener filter and M-step over given samples, a replayed MH
+    chain with the default kernel and with the team kernel, then the sample store: stored variances, streaming M-step and
+    streaming Wiener filter against the oracle from the chain's own samples.  (The body of
+    test_split_mode_kernels_against_the_oracle, for any decoder shape inputs() takes.)"""
+    from dispatch_model import shape_class
+    F, K, R = c.F, c.K, c.R
+    nu = len(c.counts)
+    sc = shape_class(F, K, "bf16x3", n_wave_tiles(c), R, n_cus())
+    eng = engine(c, "bf16x3")
+    assert eng.Fs == sc["Fs"] == query(eng, "Q_FS") and eng.Kp == sc["Kp"], (eng.Fs, sc["Fs"], eng.Kp, sc["Kp"])
+    NT = c.NT
+    eng.Zs.copy_(torch.from_numpy(c.Zs))
+    # 1. decoder
+    Vs = eng.decode(R).cpu().numpy()
+    ref = decoder_of(c, c.Zs)
+    e = rel_err(Vs[:, :, :F], ref)
+    print("decode F=%d: %.2e" % (F, e))
+    assert e < 2e-4, ("decode", e)
+    assert np.all(Vs[:, :, F:] == 0), "decode: padding bins not zero"
+    # 2. Wiener filter from the given samples
+    oracles = [oracle_at(c, eng, u, c.Zs) for u in range(nu)]
+    wiener_against(c, eng, oracles, eng.wiener(R, want_masks=True), 5e-4, "decoding")
+    # 3. M-step and cost
+    eng.m_step(R)
+    m_step_against(c, eng, oracles, R, eng.cost_from_frames(R), 1e-3, 2e-4, "decoding M-step")
+    # 4. one replayed chain from this state: the oracle's trace first (it alone says which frames are comparable)
+    refs = chain_references(c, lambda u: oracle_at(c, eng, u))
+    lo = left_out(refs)
+    print("chain F=%d K=%d: frames left out %.1f %%" % (F, K, 100 * lo))
+    assert lo <= 0.15, ("frames left out", lo)
+    dev = eng.device
+    for team in (False, True):
+        with env(VAENMF_TEAM_CHAIN="1" if team else "0"):
+            eng.Z.copy_(torch.from_numpy(c.Z0))
+            eng.Zs.zero_()
+            acc = eng.mh_chain(c.ns, c.S_steps - c.ns, 0.01, eps=torch.from_numpy(c.eps).to(dev), u=torch.from_numpy(c.uu).to(dev),
+                               want_acc=True).cpu().numpy()
+            assert query(eng, "Q_CHAIN_KERNEL") == (0 if team else sc["chain_kernel"]), (team, query(eng, "Q_CHAIN_KERNEL"), sc["chain_kernel"])
+        for sl, ref_acc, Zs_ref, keep in refs:
+            ea = float(np.max(np.abs(acc[:, sl] - ref_acc)))
+            ez = float(np.max(np.abs(eng.Zs[sl, :c.ns, :c.L].cpu().numpy()[keep] - Zs_ref[keep]), initial=0.0))
+            ezl = float(np.max(np.abs(eng.Z[sl, :c.L].cpu().numpy()[keep] - Zs_ref[keep, -1]), initial=0.0))
+            print("chain F=%d K=%d team=%d: acc %.2e Zs %.2e Z %.2e" % (F, K, team, ea, ez, ezl))
+            assert ea < 3e-3 and ez < 1e-5 and ezl < 1e-5, (team, ea, ez, ezl)
+    # 5. the sample store: chains with the device generator, with burn-in and without
+    eng.sample_store(True)
+    for call, (ns, bi) in enumerate(((10, 4), (7, 0))):
+        eng.mh_chain(ns, bi, 0.01, call=call)
+        assert query(eng, "Q_CHAIN_KERNEL") == sc["chain_kernel"], (query(eng, "Q_CHAIN_KERNEL"), sc["chain_kernel"])
+        Zc = eng.Zs[:, :ns].cpu().numpy().copy()
+        got = eng.stored_variances(ns).cpu().numpy()
+        ref = decoder_of(c, Zc)
+        e = rel_err(got[:, :, :F], ref)
+        print("store F=%d (%d, %d): %.2e" % (F, ns, bi, e))
+        assert np.all(np.isfinite(got)) and e < 2e-4, ("store", ns, bi, e)
+        oracles = [oracle_at(c, eng, u, Zc) for u in range(nu)]
+        eng.m_step_stored()
+        assert query(eng, "Q_W_FUSED") == sc["w_fused"] == 0, (query(eng, "Q_W_FUSED"), sc["w_fused"])
+        m_step_against(c, eng, oracles, ns, eng.cost_from_frames(ns), 1e-3, 2e-4, "stored M-step (%d, %d)" % (ns, bi))
+        wiener_against(c, eng, oracles, eng.wiener_stored(want_masks=True), 5e-4, "stored (%d, %d)" % (ns, bi))
+    eng.sample_store(False)
+    assert query(eng, "Q_MSTEP_PATH") == 0, query(eng, "Q_MSTEP_PATH")      # (no fused run: the path was the caller's)
+
+
+def fused_run_case(c, precision="bf16x3"):
+    """BatchEngine.run() (the sample store on by default) on a three-utterance case of inputs(): finite, bit-identical to
+    the same run stepped through mh_chain / m_step_stored / wiener_stored, and the middle utterance alone gives the bits it
+    gives inside the batch.  (The body of test_fused_run_at_other_bin_counts, for any decoder shape and precision.)"""
+    F = c.F
+    seeds = [5, 6, 7]
+    niter, nsE, biE, nsW, biW = 3, 6, 5, 12, 7
+
+    def prep(idx):
+        eng = make_engine(c.params, F, c.K, [c.counts[i] for i in idx], Rcap=12, precision=precision, seeds=[seeds[i] for i in idx])
+        eng.set_spectrogram([c.Xs[i] for i in idx])
+        eng.init_nmf([c.W0[i] for i in idx], [c.H0[i] for i in idx])
+        eng.Z.copy_(torch.from_numpy(np.concatenate([c.Z0[c.off[i]:c.off[i + 1]] for i in idx])))
+        return eng
+
+    eng = prep([0, 1, 2])
+    cost, S, N = eng.run(niter, nsE, biE, nsW, biW, 0.01)
+    assert query(eng, "Q_MSTEP_PATH") == 1, query(eng, "Q_MSTEP_PATH")
+    assert bool(torch.isfinite(cost).all()) and bool(torch.isfinite(S).all()) and bool(torch.isfinite(N).all()), "run(): non-finite results"
+    assert float(S.abs().max()) > 0 and float(S[:, F:].abs().max() if eng.Fs > F else 0) == 0, "run(): S_hat empty, or its padding not zero"
+    eng2 = prep([0, 1, 2])
+    eng2.sample_store(True)
+    c2 = np.zeros((3, niter))
+    for it in range(niter):
+        eng2.mh_chain(nsE, biE, 0.01, call=it)
+        eng2.m_step_stored()
+        c2[:, it] = eng2.cost_from_frames(nsE)
+    eng2.mh_chain(nsW, biW, 0.01, call=niter, update_Z=False)
+    S2, N2, _, _ = eng2.wiener_stored()
+    assert torch.equal(S, S2) and torch.equal(N, N2), "run() and the stepped calls differ in S_hat / N_hat"
+    assert np.max(np.abs(c2 - cost.cpu().numpy()) / np.abs(c2)) < 1e-12, ("cost of run() and of the stepped calls", c2, cost)
+    eng3 = prep([1])
+    cost3, S3, N3 = eng3.run(niter, nsE, biE, nsW, biW, 0.01)
+    sl = eng.utt_slice(1)
+    assert torch.equal(S[sl], S3) and torch.equal(N[sl], N3) and np.array_equal(cost[1].cpu().numpy(), cost3.cpu().numpy()[0]), \
+        "the middle utterance alone differs from itself inside the batch"
+    return eng, eng2
+
+
+def bench_mode_case(c):
+    """bf16 mode at one case of inputs(): decoding kernel; a replayed chain with every chain kernel the shape has
+    (first-step log-acceptances against the oracle, wave against team kernel, four-wavefront against one-wavefront form);
+    the stored M-step and Wiener filter against the oracle's from the chain's own samples, with every W-statistics kernel
+    the shape has.  (The body of test_bench_mode_kernels_against_the_oracle, for any decoder shape inputs() takes.)"""
+    from dispatch_model import shape_class
+    F, K, R = c.F, c.K, c.R
+    sc = shape_class(F, K, "bf16", n_wave_tiles(c), R, n_cus())
+    NT, nu = c.NT, len(c.counts)
+
+    def fresh():
+        eng = engine(c, "bf16", seeds=[3, 4, 5])
+        eng.Z.copy_(torch.from_numpy(c.Z0))
+        return eng
+
+    # 7. decoder
+    eng = fresh()
+    assert eng.Fs == sc["Fs"] == query(eng, "Q_FS") and eng.Kp == sc["Kp"], (eng.Fs, sc["Fs"], eng.Kp, sc["Kp"])
+    eng.Zs.copy_(torch.from_numpy(c.Zs))
+    Vs = eng.decode(R).cpu().numpy()
+    e = rel_err(Vs[:, :, :F], decoder_of(c, c.Zs))
+    print("decode bf16 F=%d: %.2e" % (F, e))
+    assert e < 5e-2 and np.all(Vs[:, :, F:] == 0), ("decode bf16", e)
+
+    def chain(**kv):
+        with env(**kv):
+            eng = fresh()
+            acc = eng.mh_chain(c.ns, c.S_steps - c.ns, 0.01, eps=torch.from_numpy(c.eps).to(eng.device),
+                               u=torch.from_numpy(c.uu).to(eng.device), want_acc=True).cpu().numpy()
+            return acc, eng.Zs[:, :c.ns].cpu().numpy().copy(), eng.Z.cpu().numpy().copy(), query(eng, "Q_CHAIN_KERNEL")
+
+    dflt, team = chain(), chain(VAENMF_TEAM_CHAIN="1")
+    assert dflt[3] == sc["chain_kernel"] and team[3] == 0, (dflt[3], sc["chain_kernel"], team[3])
+    assert np.all(np.isfinite(dflt[0])) and np.all(np.isfinite(team[0])), "log-acceptances not finite"
+    refs = chain_references(c, lambda u: initial_oracle(c, u))
+    for u, (sl, ref_acc, _, _) in enumerate(refs):
+        # (only the first step is comparable for every frame: afterwards a chain whose decision differs is in another state)
+        for name, out in (("default", dflt), ("team", team)):
+            e = float(np.max(np.abs(out[0][0, sl] - ref_acc[0])))
+            print("chain bf16 F=%d K=%d utt %d %s: first-step acc %.3f" % (F, K, u, name, e))
+            assert e < 0.5, (name, u, e)
+    if sc["chain_kernel"]:
+        e = float(np.max(np.abs(dflt[0] - team[0])))
+        print("chain bf16 F=%d K=%d: wave - team %.3f" % (F, K, e))
+        assert e < 0.1, ("wave - team", e)
+
+    # 8. / 9. the store: chain, streaming M-step, streaming Wiener filter
+    def stored(**kv):
+        with env(**kv):
+            eng = fresh()
+            eng.sample_store(True)
+            acc = eng.mh_chain(R, 4, 0.01, call=0, want_acc=True)
+            r = SimpleNamespace(eng=eng, chain_kernel=query(eng, "Q_CHAIN_KERNEL"), acc=acc.cpu().numpy(), Z=eng.Z.cpu().numpy().copy(),
+                                Zs=eng.Zs[:, :R].cpu().numpy().copy(), rows=eng.stored_variances(R).cpu().numpy())
+            r.oracles = [oracle_at(c, eng, u, r.Zs) for u in range(nu)]
+            r.cf = eng.m_step_stored().cpu().numpy().copy()
+            r.w_fused = query(eng, "Q_W_FUSED")
+            r.cost = eng.cost_from_frames(R)
+            r.upd = [t.cpu().numpy().copy() for t in (eng.W, eng.Ht, eng.g)] + [r.cf]
+            r.wf = eng.wiener_stored(want_masks=True)
+            return r
+
+    a = stored()
+    assert a.chain_kernel == sc["chain_kernel"] and a.w_fused == sc["w_fused"], (a.chain_kernel, sc["chain_kernel"], a.w_fused, sc["w_fused"])
+    assert query(a.eng, "Q_MSTEP_PATH") == 0, query(a.eng, "Q_MSTEP_PATH")
+    assert np.all(np.isfinite(a.rows)) and np.abs(a.Zs - c.Z0[:, None, :]).max() > 0.05, "stored rows not finite, or the chain did not move"
+    m_step_against(c, a.eng, a.oracles, R, a.cost, 3e-2, 3e-3, "bench M-step")
+    wiener_against(c, a.eng, a.oracles, a.wf, 1e-2, "bench stored", absolute=True)
+    names = ("W", "Ht", "g", "cost")
+    if sc["w_fused"] == 2:
+        b = stored(VAENMF_WGROUP="0")          # the tile kernel: bit for bit (test_group_w_statistics_equal_the_tile_kernel_bit_for_bit)
+        assert b.w_fused == 1, b.w_fused
+        for x, y, name in zip(a.upd, b.upd, names):
+            assert np.array_equal(x, y), name
+        b = stored(VAENMF_WFUSED="0")          # the two-kernel path: the order of the float sums over frames (2e-5)
+        assert b.w_fused == 0, b.w_fused
+        for x, y, name in zip(a.upd, b.upd, names):
+            e = float(np.max(np.abs(x - y) / (np.abs(y) + 1e-20)))
+            print("W statistics F=%d fused - two kernels %s: %.2e" % (F, name, e))
+            assert e < 2e-5, name
+    if sc["chain_kernel"] == 2:
+        b = stored(VAENMF_WCHAIN4="0")         # the one-wavefront form: bit for bit
+        assert b.chain_kernel == 1, b.chain_kernel
+        d = chain(VAENMF_WCHAIN4="0")
+        assert d[3] == 1, d[3]
+        for x, y, name in zip(dflt[:3], d[:3], ("acc", "Zs", "Z")):
+            assert np.array_equal(x, y), "replayed " + name
+        for x, y, name in zip([a.acc, a.Zs, a.Z, a.rows] + a.upd, [b.acc, b.Zs, b.Z, b.rows] + b.upd, ("acc", "Zs", "Z", "rows") + names):
+            assert np.array_equal(x, y), name
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -64,7 +64,7 @@ def test_bf16_rne_denormals_zeros_and_the_largest_value():
     assert np.all(np.abs(t) <= np.abs(r[np.isfinite(r)].astype(np.float64)))
 
 
-SHAPES = sorted({(F, zd, hd, Dy) for _, F, zd, hd, Dy in bm.DECODE_CASES} | {(c[1], c[2], c[3], c[4]) for c in bm.CHAIN_CASES})
+SHAPES = bm.case_shapes()
 
 
 @pytest.mark.parametrize("F,z_dim,h_dim,Dy", SHAPES)

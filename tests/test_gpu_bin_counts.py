@@ -12,8 +12,6 @@ Tolerances are the ones tests/test_gpu_parity.py states for the same operations 
 test_m_step_and_chain_other_shapes, test_bench_mode_m_step_against_the_oracle, test_wave_chain_bf16_mode,
 test_stored_m_step_and_wiener_match_the_decoding_ones, test_fused_w_statistics_equal_the_two_kernel_path).
 """
-from types import SimpleNamespace
-
 import numpy as np
 import pytest
 import torch
@@ -21,7 +19,7 @@ import torch
 import vaenmf_oracle as orc
 import em_support as es
 from dispatch_model import COUNTS, N_WAVE_TILES, shape_class
-from em_support import RecordingRNG, make_engine
+from em_support import RecordingRNG
 from helpers import GOLDEN, need_gpu, nrm_err, rel_err
 
 gpu = pytest.mark.gpu        # (per test, not per module: test_sweep_reaches_every_dispatch_class runs without a GPU)
@@ -123,73 +121,7 @@ def test_split_mode_kernels_against_the_oracle(F, K, R):
     default kernel and with the team kernel, then the sample store: stored variances, streaming M-step and streaming
     Wiener filter against the oracle from the chain's own samples."""
     need_gpu()
-    c = es.inputs(F, K, R)
-    sc = shape_class(F, K, "bf16x3", N_WAVE_TILES, R, es.n_cus())
-    eng = es.engine(c, "bf16x3")
-    assert eng.Fs == sc["Fs"] == es.query(eng, "Q_FS") and eng.Kp == sc["Kp"]
-    NT = c.NT
-    eng.Zs.copy_(torch.from_numpy(c.Zs))
-    # 1. decoder
-    Vs = eng.decode(R).cpu().numpy()
-    ref = orc.decoder_forward(c.params, c.Zs.reshape(-1, 32)).reshape(NT, R, F)
-    e = rel_err(Vs[:, :, :F], ref)
-    print("decode F=%d: %.2e" % (F, e))
-    assert e < 2e-4
-    assert np.all(Vs[:, :, F:] == 0)
-    # 2. Wiener filter from the given samples
-    oracles = [es.oracle_at(c, eng, u, c.Zs) for u in range(len(COUNTS))]
-    es.wiener_against(c, eng, oracles, eng.wiener(R, want_masks=True), 5e-4, "decoding")
-    # 3. M-step and cost
-    eng.m_step(R)
-    es.m_step_against(c, eng, oracles, R, eng.cost_from_frames(R), 1e-3, 2e-4, "decoding M-step")
-    # 4. one replayed chain from this state: the oracle's trace first (it alone says which frames are comparable)
-    refs = []
-    for u in range(len(COUNTS)):
-        sl = eng.utt_slice(u)
-        o = es.oracle_at(c, eng, u)
-        draws = []
-        for m in range(c.S_steps):
-            draws += [c.eps[m, sl].T.copy(), c.uu[m, sl].copy()]
-        o.rng = orc.ReplayRNG(draws)
-        tr = []
-        Zs_ref = o.sample_posterior(c.Z0[sl].T.copy(), c.ns, c.S_steps - c.ns, trace=tr)
-        ref_acc = np.stack([t["acc"] for t in tr])
-        keep = np.abs(np.log(c.uu[:, sl]) - ref_acc).min(0) > 1e-2       # decisions are only comparable away from the threshold
-        refs.append((sl, ref_acc, Zs_ref, keep))
-    left_out = 1.0 - np.concatenate([r[3] for r in refs]).mean()
-    print("chain F=%d K=%d: frames left out %.1f %%" % (F, K, 100 * left_out))
-    assert left_out <= 0.15
-    dev = eng.device
-    for team in (False, True):
-        with es.env(VAENMF_TEAM_CHAIN="1" if team else "0"):
-            eng.Z.copy_(torch.from_numpy(c.Z0))
-            eng.Zs.zero_()
-            acc = eng.mh_chain(c.ns, c.S_steps - c.ns, 0.01, eps=torch.from_numpy(c.eps).to(dev), u=torch.from_numpy(c.uu).to(dev),
-                               want_acc=True).cpu().numpy()
-            assert es.query(eng, "Q_CHAIN_KERNEL") == (0 if team else sc["chain_kernel"])
-        for sl, ref_acc, Zs_ref, keep in refs:
-            ea = float(np.max(np.abs(acc[:, sl] - ref_acc)))
-            ez = float(np.max(np.abs(eng.Zs[sl, :c.ns].cpu().numpy()[keep] - Zs_ref[keep]), initial=0.0))
-            ezl = float(np.max(np.abs(eng.Z[sl].cpu().numpy()[keep] - Zs_ref[keep, -1]), initial=0.0))
-            print("chain F=%d K=%d team=%d: acc %.2e Zs %.2e Z %.2e" % (F, K, team, ea, ez, ezl))
-            assert ea < 3e-3 and ez < 1e-5 and ezl < 1e-5, (team, ea, ez, ezl)
-    # 5. the sample store: chains with the device generator, with burn-in and without
-    eng.sample_store(True)
-    for call, (ns, bi) in enumerate(((10, 4), (7, 0))):
-        eng.mh_chain(ns, bi, 0.01, call=call)
-        assert es.query(eng, "Q_CHAIN_KERNEL") == sc["chain_kernel"]
-        Zc = eng.Zs[:, :ns].cpu().numpy().copy()
-        got = eng.stored_variances(ns).cpu().numpy()
-        ref = orc.decoder_forward(c.params, Zc.reshape(-1, 32)).reshape(NT, ns, F)
-        e = rel_err(got[:, :, :F], ref)
-        print("store F=%d (%d, %d): %.2e" % (F, ns, bi, e))
-        assert np.all(np.isfinite(got)) and e < 2e-4
-        oracles = [es.oracle_at(c, eng, u, Zc) for u in range(len(COUNTS))]
-        eng.m_step_stored()
-        assert es.query(eng, "Q_W_FUSED") == sc["w_fused"] == 0
-        es.m_step_against(c, eng, oracles, ns, eng.cost_from_frames(ns), 1e-3, 2e-4, "stored M-step (%d, %d)" % (ns, bi))
-        es.wiener_against(c, eng, oracles, eng.wiener_stored(want_masks=True), 5e-4, "stored (%d, %d)" % (ns, bi))
-    eng.sample_store(False)
+    es.split_mode_case(es.inputs(F, K, R))
 
 
 @gpu
@@ -198,37 +130,7 @@ def test_fused_run_at_other_bin_counts(F):
     """BatchEngine.run() (the sample store on by default): finite, bit-identical to the same run stepped through mh_chain /
     m_step_stored / wiener_stored, and the middle utterance alone gives the bits it gives inside the batch."""
     need_gpu()
-    c = es.inputs(F, 10, 12)
-    seeds = [5, 6, 7]
-    niter, nsE, biE, nsW, biW = 3, 6, 5, 12, 7
-
-    def prep(idx):
-        eng = make_engine(c.params, F, c.K, [COUNTS[i] for i in idx], Rcap=12, seeds=[seeds[i] for i in idx])
-        eng.set_spectrogram([c.Xs[i] for i in idx])
-        eng.init_nmf([c.W0[i] for i in idx], [c.H0[i] for i in idx])
-        eng.Z.copy_(torch.from_numpy(np.concatenate([c.Z0[c.off[i]:c.off[i + 1]] for i in idx])))
-        return eng
-
-    eng = prep([0, 1, 2])
-    cost, S, N = eng.run(niter, nsE, biE, nsW, biW, 0.01)
-    assert es.query(eng, "Q_MSTEP_PATH") == 1
-    assert bool(torch.isfinite(cost).all()) and bool(torch.isfinite(S).all()) and bool(torch.isfinite(N).all())
-    assert float(S.abs().max()) > 0 and float(S[:, F:].abs().max() if eng.Fs > F else 0) == 0
-    eng2 = prep([0, 1, 2])
-    eng2.sample_store(True)
-    c2 = np.zeros((3, niter))
-    for it in range(niter):
-        eng2.mh_chain(nsE, biE, 0.01, call=it)
-        eng2.m_step_stored()
-        c2[:, it] = eng2.cost_from_frames(nsE)
-    eng2.mh_chain(nsW, biW, 0.01, call=niter, update_Z=False)
-    S2, N2, _, _ = eng2.wiener_stored()
-    assert torch.equal(S, S2) and torch.equal(N, N2)
-    assert np.max(np.abs(c2 - cost.cpu().numpy()) / np.abs(c2)) < 1e-12
-    eng3 = prep([1])
-    cost3, S3, N3 = eng3.run(niter, nsE, biE, nsW, biW, 0.01)
-    sl = eng.utt_slice(1)
-    assert torch.equal(S[sl], S3) and torch.equal(N[sl], N3) and np.array_equal(cost[1].cpu().numpy(), cost3.cpu().numpy()[0])
+    es.fused_run_case(es.inputs(F, 10, 12))
 
 
 @gpu
@@ -239,97 +141,7 @@ def test_bench_mode_kernels_against_the_oracle(F, K, R):
     stored M-step and Wiener filter against the oracle's from the chain's own samples, with every W-statistics kernel the
     shape has."""
     need_gpu()
-    c = es.inputs(F, K, R)
-    sc = shape_class(F, K, "bf16", N_WAVE_TILES, R, es.n_cus())
-    NT, nu = c.NT, len(COUNTS)
-
-    def fresh():
-        eng = es.engine(c, "bf16", seeds=[3, 4, 5])
-        eng.Z.copy_(torch.from_numpy(c.Z0))
-        return eng
-
-    # 7. decoder
-    eng = fresh()
-    assert eng.Fs == sc["Fs"] == es.query(eng, "Q_FS") and eng.Kp == sc["Kp"]
-    eng.Zs.copy_(torch.from_numpy(c.Zs))
-    Vs = eng.decode(R).cpu().numpy()
-    e = rel_err(Vs[:, :, :F], orc.decoder_forward(c.params, c.Zs.reshape(-1, 32)).reshape(NT, R, F))
-    print("decode bf16 F=%d: %.2e" % (F, e))
-    assert e < 5e-2 and np.all(Vs[:, :, F:] == 0)
-
-    def chain(**env):
-        with es.env(**env):
-            eng = fresh()
-            acc = eng.mh_chain(c.ns, c.S_steps - c.ns, 0.01, eps=torch.from_numpy(c.eps).to(eng.device),
-                               u=torch.from_numpy(c.uu).to(eng.device), want_acc=True).cpu().numpy()
-            return acc, eng.Zs[:, :c.ns].cpu().numpy().copy(), eng.Z.cpu().numpy().copy(), es.query(eng, "Q_CHAIN_KERNEL")
-
-    dflt, team = chain(), chain(VAENMF_TEAM_CHAIN="1")
-    assert dflt[3] == sc["chain_kernel"] and team[3] == 0
-    assert np.all(np.isfinite(dflt[0])) and np.all(np.isfinite(team[0]))
-    for u in range(nu):
-        sl = slice(c.off[u], c.off[u + 1])
-        o = orc.MCEMOracle("M1", 1)
-        o.init_parameters(c.Xs[u], c.params, K, 1e-8, orc.NumpyRNG(0), W0=c.W0[u], H0=c.H0[u])
-        o.g = c.gains[sl].copy()
-        draws = []
-        for m in range(c.S_steps):
-            draws += [c.eps[m, sl].T.copy(), c.uu[m, sl].copy()]
-        o.rng = orc.ReplayRNG(draws)
-        tr = []
-        o.sample_posterior(c.Z0[sl].T.copy(), c.ns, c.S_steps - c.ns, trace=tr)
-        # (only the first step is comparable for every frame: afterwards a chain whose decision differs is in another state)
-        for name, out in (("default", dflt), ("team", team)):
-            e = float(np.max(np.abs(out[0][0, sl] - tr[0]["acc"])))
-            print("chain bf16 F=%d K=%d utt %d %s: first-step acc %.3f" % (F, K, u, name, e))
-            assert e < 0.5
-    if sc["chain_kernel"]:
-        e = float(np.max(np.abs(dflt[0] - team[0])))
-        print("chain bf16 F=%d K=%d: wave - team %.3f" % (F, K, e))
-        assert e < 0.1
-
-    # 8. / 9. the store: chain, streaming M-step, streaming Wiener filter
-    def stored(**env):
-        with es.env(**env):
-            eng = fresh()
-            eng.sample_store(True)
-            acc = eng.mh_chain(R, 4, 0.01, call=0, want_acc=True)
-            r = SimpleNamespace(eng=eng, chain_kernel=es.query(eng, "Q_CHAIN_KERNEL"), acc=acc.cpu().numpy(), Z=eng.Z.cpu().numpy().copy(),
-                                Zs=eng.Zs[:, :R].cpu().numpy().copy(), rows=eng.stored_variances(R).cpu().numpy())
-            r.oracles = [es.oracle_at(c, eng, u, r.Zs) for u in range(nu)]
-            r.cf = eng.m_step_stored().cpu().numpy().copy()
-            r.w_fused = es.query(eng, "Q_W_FUSED")
-            r.cost = eng.cost_from_frames(R)
-            r.upd = [t.cpu().numpy().copy() for t in (eng.W, eng.Ht, eng.g)] + [r.cf]
-            r.wf = eng.wiener_stored(want_masks=True)
-            return r
-
-    a = stored()
-    assert a.chain_kernel == sc["chain_kernel"] and a.w_fused == sc["w_fused"]
-    assert np.all(np.isfinite(a.rows)) and np.abs(a.Zs - c.Z0[:, None, :]).max() > 0.05
-    es.m_step_against(c, a.eng, a.oracles, R, a.cost, 3e-2, 3e-3, "bench M-step")
-    es.wiener_against(c, a.eng, a.oracles, a.wf, 1e-2, "bench stored", absolute=True)
-    names = ("W", "Ht", "g", "cost")
-    if sc["w_fused"] == 2:
-        b = stored(VAENMF_WGROUP="0")          # the tile kernel: bit for bit (test_group_w_statistics_equal_the_tile_kernel_bit_for_bit)
-        assert b.w_fused == 1
-        for x, y, name in zip(a.upd, b.upd, names):
-            assert np.array_equal(x, y), name
-        b = stored(VAENMF_WFUSED="0")          # the two-kernel path: the order of the float sums over frames (2e-5)
-        assert b.w_fused == 0
-        for x, y, name in zip(a.upd, b.upd, names):
-            e = float(np.max(np.abs(x - y) / (np.abs(y) + 1e-20)))
-            print("W statistics F=%d fused - two kernels %s: %.2e" % (F, name, e))
-            assert e < 2e-5, name
-    if sc["chain_kernel"] == 2:
-        b = stored(VAENMF_WCHAIN4="0")         # the one-wavefront form: bit for bit
-        assert b.chain_kernel == 1
-        d = chain(VAENMF_WCHAIN4="0")
-        assert d[3] == 1
-        for x, y, name in zip(dflt[:3], d[:3], ("acc", "Zs", "Z")):
-            assert np.array_equal(x, y), "replayed " + name
-        for x, y, name in zip([a.acc, a.Zs, a.Z, a.rows] + a.upd, [b.acc, b.Zs, b.Z, b.rows] + b.upd, ("acc", "Zs", "Z", "rows") + names):
-            assert np.array_equal(x, y), name
+    es.bench_mode_case(es.inputs(F, K, R))
 
 
 @gpu
