@@ -13,7 +13,12 @@
  *   - every function returns 0 on success or a negative code; vaenmf_last_error()
  *     returns a thread-local message.  Nothing throws.
  *   - `stream` is a hipStream_t passed as void* (0 = default stream).  All work is
- *     enqueued asynchronously; no call synchronises the device unless stated.
+ *     enqueued asynchronously; no call synchronises the device unless stated.  Every kernel, memset and copy of a call goes
+ *     to the stream it is given and to no other, the null stream included; a call that does not say that it waits returns
+ *     while its stream is still busy, and -- once the tables of its first use are on the device -- may be made while the
+ *     caller captures that stream into a graph: device buffers, maps and seeds are read when the graph runs, host tables and
+ *     scalars when it is captured.  Two calls may not be captured: vaenmf_em_run and vaenmf_bind_batch_async (see there).
+ *     tests/test_gpu_streams.py holds every entry point to this paragraph.
  *   - pointers marked DEV are device pointers owned by the caller (e.g. the
  *     PyTorch-ROCm allocator), never freed by the callee.  Required alignment: 16 bytes, and no more: the rows of X, X2,
  *     Vb, W, Ht, Z, Zs, B1, the replay draws and every [..][Fs] output are read and written with 16-byte vector accesses,
@@ -167,7 +172,10 @@ int vaenmf_bind_batch(vaenmf_plan* p, int32_t n_utt, const int32_t* frame_offset
  * synchronises (results collected later) can prepare batch k+1 while batch k runs.  A batch with
  * another frame structure synchronises `stream` and uploads the tables as vaenmf_bind_batch does.
  * STREAM CONTRACT: the seed upload is ordered on `stream` only -- the calls that consume the batch (vaenmf_mh_chain,
- * vaenmf_em_run, ...) must be enqueued on the same stream, or after an event / synchronisation that orders them behind it. */
+ * vaenmf_em_run, ...) must be enqueued on the same stream, or after an event / synchronisation that orders them behind it.
+ * The pinned slot of the seeds is one of a ring of eight, guarded by an event the call records on `stream` and waits for
+ * eight binds later: the call may not be called while a caller's stream capture is open (an event recorded into a graph cannot
+ * be waited for), and a ninth bind behind work that has not run waits for the first. */
 int vaenmf_bind_batch_async(vaenmf_plan* p, int32_t n_utt, const int32_t* frame_offsets,
                             const uint64_t* utt_seeds, void* stream);
 
@@ -250,7 +258,8 @@ int vaenmf_wiener(vaenmf_plan* p, const float* X2, const float* W, const float* 
  * been forgotten starts over with a launch-by-launch call.  The batch's contents (spectrogram,
  * seeds, frame tables) sit behind the same pointers and are read at run time.  Profiling
  * (vaenmf_profile_*) and VAENMF_GRAPH=0 keep the launch-by-launch path; results are the same
- * either way. */
+ * either way.  The graphs are captured on a stream of the plan's own and launched on `stream`: vaenmf_em_run itself may not be
+ * called while a caller's stream capture is open. */
 int vaenmf_em_run(vaenmf_plan* p, const float* X2, float* W, float* Ht, float* g, float* Z,
                   const float* B1, float* Zs, int32_t Rcap, int32_t niter,
                   int32_t nsE, int32_t biE, int32_t nsWF, int32_t biWF, float var_rw,

@@ -15,55 +15,21 @@ EVERY library call:
 No tolerance: poison, alignment and exact extents must change nothing.  A read by an idle lane of a row it shadows cannot
 be seen here -- a read whose value reaches no output leaves no trace; reads are caught through changed results only.
 
-CONTRACT and BUFFERS below are written from include/vaenmf.h, not from the kernels."""
-from collections import namedtuple
+CONTRACT and BUFFERS (tests/contract_cases.py, shared with tests/stream_cases.py) are written from include/vaenmf.h, not from
+the kernels."""
 from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
-from contract_cases import BURNIN, BY_NAME, CASES, DECODE_CASES, DECODE_SAMPLES, NS, RCAP, VAR_RW, case_class, inputs, is_wide
+from contract_cases import (BUFFERS, BURNIN, BY_NAME, CASES, CONTRACT, DECODE_CASES, DECODE_SAMPLES, NS, RCAP, VAR_RW, case_class, inputs,
+                            is_wide)
 from em_support import make_engine, query
 from guarded import POISON, Arena, GuardError, bits, make_guarded_engine, power_spec, same_bits
 from helpers import need_gpu
 
 pytestmark = pytest.mark.gpu
-
-# entry point -> buffers it reads (const in the header), buffers it writes.  Everything it does not write it leaves alone.
-E = namedtuple("E", "reads writes")
-CONTRACT = {
-    "vaenmf_power_spec": E(("X",), ("X2",)),
-    "vaenmf_layer1_bias": E(("y",), ("B1",)),
-    "vaenmf_init_nmf": E((), ("W", "Ht", "g")),
-    "vaenmf_rng_fill": E((), ("eps", "u")),
-    # Z when update_Z != 0, Zs unless NULL, acc_out unless NULL; the sample-variance store is the plan's own memory
-    "vaenmf_mh_chain": E(("X2", "W", "Ht", "g", "B1", "Vb", "eps", "u"), ("Z", "Zs", "acc")),
-    "vaenmf_sample_store_gather": E((), ("Vs_store",)),
-    "vaenmf_m_step_stored": E(("X2", "Vb"), ("W", "Ht", "g", "cost_frames")),       # with a fixed noise PSD: g and cost_frames only
-    "vaenmf_wiener_stored": E(("W", "Ht", "g", "X", "Vb"), ("S_hat", "N_hat", "WFs", "WFn")),
-    "vaenmf_decode": E(("Zs", "B1"), ("Vs",)),
-    "vaenmf_m_step": E(("X2", "Zs", "B1", "Vb"), ("W", "Ht", "g", "cost_frames")),
-    "vaenmf_wiener": E(("X2", "W", "Ht", "g", "Zs", "B1", "X", "Vb"), ("S_hat", "N_hat", "WFs", "WFn")),
-    "vaenmf_em_run": E(("X2", "B1", "X", "Vb"), ("W", "Ht", "g", "Z", "Zs", "S_hat", "N_hat", "cost")),
-}
-# buffer -> (documented extent, padding written as zero, padding left alone); d: F, K, L, ns.  Padding in neither list is
-# unspecified after a write (X2 of vaenmf_power_spec, Vs of vaenmf_sample_store_gather, the draws' columns L..Lp-1)
-_all = lambda t, d: t
-BUFFERS = {
-    "X2": (lambda t, d: t[:, :d.F], (), ()),
-    "B1": (_all, (), ()), "g": (_all, (), ()), "u": (_all, (), ()), "acc": (_all, (), ()), "cost_frames": (_all, (), ()), "cost": (_all, (), ()),
-    "W": (lambda t, d: t[:, :d.F, :d.K], (lambda t, d: t[:, d.F:], lambda t, d: t[:, :, d.K:]), ()),
-    "Ht": (lambda t, d: t[:, :d.K], (lambda t, d: t[:, d.K:],), ()),
-    "Z": (lambda t, d: t[:, :d.L], (lambda t, d: t[:, d.L:],), ()),
-    "Zs": (lambda t, d: t[:, :d.ns, :d.L], (lambda t, d: t[:, :d.ns, d.L:],), (lambda t, d: t[:, d.ns:],)),
-    "eps": (lambda t, d: t[:, :, :d.L], (), ()),
-    "Vs_store": (lambda t, d: t[:, :, :d.F], (), ()),
-    "Vs": (lambda t, d: t[:, :, :d.F], (lambda t, d: t[:, :, d.F:],), ()),
-    "S_hat": (lambda t, d: t[:, :d.F], (lambda t, d: t[:, d.F:],), ()), "N_hat": (lambda t, d: t[:, :d.F], (lambda t, d: t[:, d.F:],), ()),
-    "WFs": (lambda t, d: t[:, :d.F], (lambda t, d: t[:, d.F:],), ()), "WFn": (lambda t, d: t[:, :d.F], (lambda t, d: t[:, d.F:],), ()),
-}
-
 
 class Pair:
     """A guarded engine and its twin, and the buffers of both by their names in CONTRACT."""
