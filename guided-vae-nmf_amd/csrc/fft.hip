@@ -8,6 +8,8 @@
 //     circular convolution of power-of-two length m >= 2n-1 through the radix-2 fft_lds (16 m bytes of LDS, 128 KiB at
 //     m = 8192); the chirp, the m-point twiddles and the spectrum of the conjugate chirp come from global tables.
 // Tables are built once per (device, n) on the host in long double, rounded to double and uploaded once.
+// Reflect padding follows np.pad(mode="reflect") at any signal length, also when the end-padded signal is shorter than
+// the n_fft / 2 samples of padding and the position bounces more than once (reflect_index).
 #include <math.h>
 #include <map>
 #include <mutex>
@@ -43,15 +45,28 @@ __device__ __forceinline__ double2 cmul(double2 a, double2 b) {
   return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
 }
 
+// Position p of a signal of Tp samples extended by reflection about its first and last sample, as np.pad(mode="reflect")
+// extends it at any length: period 2 (Tp - 1), index 0 when Tp = 1.  One bounce at each end comes first and is all that a
+// signal with Tp > n_fft / 2 ever takes; shorter ones fold the position into one period.
+__device__ __forceinline__ int64_t reflect_index(int64_t p, int64_t Tp) {
+  if (p < 0) p = -p;
+  if (p >= Tp) p = 2 * (Tp - 1) - p;
+  if (p < 0 || p >= Tp) {
+    if (Tp <= 1) return 0;
+    const int64_t per = 2 * (Tp - 1);
+    p %= per;
+    if (p < 0) p += per;
+    if (p >= Tp) p = per - p;
+  }
+  return p;
+}
+
 // Sample t of frame i of one utterance: librosa's framing of the end-padded signal (T real samples, Tp after the end pad),
-// centre padding by reflection (about the first / last padded sample) or with zeros, or no padding at all
+// centre padding by reflection (reflect_index) or with zeros, or no padding at all
 __device__ __forceinline__ double frame_sample(const float* __restrict__ wav, int64_t off, int64_t T, int64_t Tp, int i, int t,
                                                const FrameArgs& a) {
   int64_t p = (int64_t)i * a.hop + t - (a.center ? a.nfft / 2 : 0);
-  if (a.center && a.reflect) {
-    if (p < 0) p = -p;
-    if (p >= Tp) p = 2 * (Tp - 1) - p;
-  }
+  if (a.center && a.reflect) p = reflect_index(p, Tp);
   return (p >= 0 && p < T) ? (double)wav[off + p] : 0.0;
 }
 
@@ -93,9 +108,7 @@ __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ wav
   }
   __syncthreads();
   for (int t = threadIdx.x; t < nfft; t += blockDim.x) {
-    int64_t p = (int64_t)i * hop + t - nfft / 2;  // centre=True, reflect padding
-    if (p < 0) p = -p;
-    if (p >= Tp) p = 2 * (Tp - 1) - p;
+    const int64_t p = reflect_index((int64_t)i * hop + t - nfft / 2, Tp);  // centre=True, reflect padding
     const double v = (p >= 0 && p < T) ? (double)wav[off + p] : 0.0;
     // cos(2 pi t / nfft) from the twiddle table (two thirds of this kernel's time went into a second fp64 sincospi per sample)
     const double cw = t < nfft / 2 ? twr[t] : -twr[t - nfft / 2];

@@ -318,7 +318,9 @@ int vaenmf_power_spec(const float* X, float* X2, int64_t n, void* stream);
  * frame_offsets DEV int32 [n_utt+1]; frame_utt DEV int32 [NT]; padded_len DEV int32
  * [n_utt]; X DEV complex64 [NT][Fs] (Fs >= n_fft/2+1, bins >= n_fft/2+1 zeroed); the
  * window, the centring and the pad mode come from `opts` (the reference's own: periodic
- * Hann, center, reflect padding).
+ * Hann, center, reflect padding).  Reflect padding is np.pad(mode="reflect") of the
+ * end-padded signal at any length: a signal shorter than the n_fft/2 samples of padding is
+ * reflected as often as needed (period 2 (Tp - 1); a single sample is repeated).
  * Kernels: power-of-two n_fft <= 2048 with periodic Hann, center and reflect padding run
  * the radix-2 kernels; everything else a mixed-radix (radices 2, 3, 4, 5, 7) or, for
  * lengths with a prime factor above 7, a Bluestein FFT.  Per-size twiddle / chirp tables
