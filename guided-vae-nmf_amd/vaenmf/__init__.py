@@ -6,3 +6,4 @@ from .engine import BatchEngine
 from .resample import resample, resample_batch
 from .dataset import FeatureMoments, make_test_set, make_train_set, mix_batch, plan_mixes
 from .train import Trainer, fit_classifier, fit_m1, fit_m2
+from .train_mask import MaskTrainer, fit_mask_filter, mask_spec

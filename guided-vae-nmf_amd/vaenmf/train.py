@@ -14,7 +14,8 @@ There is no CPU fallback: a Trainer needs the HIP library and a GPU.  Host-only 
 state_shapes, check_adam_state, checkpoint_name, batch_bounds, epoch_log_lines.
 
 Not built: Classifier(batch_norm=True), Classifier2Classes, the MSE losses of training_wiener_filter.py, U_loss, the HDF5
-loader, data-parallel training -- NotImplementedError where reachable."""
+loader, data-parallel training -- NotImplementedError where reachable.  (The Wiener-mask baseline with its MSE losses and
+deeper classifiers is trained by vaenmf.train_mask: MaskTrainer, fit_mask_filter.)"""
 import collections
 import ctypes as C
 import os
